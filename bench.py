@@ -19,6 +19,14 @@ scaling (BASELINE configs[3..4]): the mesh is refined to
 ~10M x N cells (h / sqrt(N)), every rank owns one vertical slab of ~10M
 cells, halos and reductions go over RCCL (xGMI); torch.distributed (gloo)
 only bootstraps the RCCL unique id and the barrier / max-time reduction.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.
+``--full`` adds what takes runs of its own (the CPU baseline, the reference's
+own criterion workloads) as extra keys of the same line.  ``--dump-outputs
+DIR`` writes the velocity and pressure the last timed step left (get_u /
+get_p) to DIR/u.npy and DIR/p.npy: the mesh and the initial state are
+deterministic, so two builds run with the same arguments are comparable
+array for array.
 """
 from __future__ import annotations
 
@@ -42,6 +50,10 @@ CONFIGS = {
     "c2": (5.449e-4, 1.0e7, 2),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# --dump-outputs: at most this many cells of u (2 x f64) and p (f64) over all
+# ranks, 48 MB, under the 64 MB a dump may take; fixed sample seed
+DUMP_MAX_CELLS = 2_000_000
+DUMP_SEED = 20240607
 
 
 def log(*a):
@@ -270,6 +282,34 @@ def reference_workloads(max_seconds=60.0, only=None):
     return out
 
 
+def dump_cells(n_cells, max_cells=DUMP_MAX_CELLS, seed=DUMP_SEED):
+    """Cells --dump-outputs writes: all of them (None) up to `max_cells`, else
+    a sorted sample of `max_cells` cell indices that depends on (n_cells,
+    max_cells, seed) alone, so two builds given the same arguments write the
+    same cells."""
+    import numpy as np
+    if n_cells <= max_cells:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n_cells, size=max_cells, replace=False))
+
+
+def dump_outputs(solver, out_dir, suffix="", max_cells=DUMP_MAX_CELLS):
+    """Write what the last step computed, as a caller of the timed path reads
+    it -- get_u() (cells x 2) and get_p() (cells), float64 -- to
+    out_dir/u<suffix>.npy and out_dir/p<suffix>.npy; returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    u = np.asarray(solver.get_u(), dtype=np.float64)
+    p = np.asarray(solver.get_p(), dtype=np.float64)
+    sel = dump_cells(p.shape[0], max_cells)
+    written = {}
+    for name, a in (("u", u), ("p", p)):
+        a = np.ascontiguousarray(a if sel is None else a[sel])
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[name + suffix] = list(a.shape)
+    return written
+
+
 def comm_timing_summary(t):
     """Per-FGMRES-iteration communication times of the extra timed step
     (cfd_comm_timing), by category: max and mean over ranks of the compute
@@ -345,10 +385,19 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--outer", type=int, default=5)
     ap.add_argument("--inner", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result's own steps also run what takes runs of its own: the CPU baseline "
+                         "(the oracle, one whole step) and the reference's own criterion workloads; without it "
+                         "the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the state the last one left, as a caller reads it "
+                         "(get_u / get_p), to DIR/u.npy and DIR/p.npy (float64; above DUMP_MAX_CELLS cells a "
+                         "fixed seeded sample of the cells)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--round", default="r06")
     ap.add_argument("--ref-workloads", type=int, default=1,
-                    help="1: also time the reference's own criterion workloads (natural convergence) as extra keys")
+                    help="with --full, 1: also time the reference's own criterion workloads (natural "
+                         "convergence) as extra keys")
     ap.add_argument("--inproc-ranks", type=int, default=0,
                     help="test mode: run the distributed solver as R in-process ranks on GPU 0 "
                          "(not a bench line; exercises the multi-GPU code path at scale on one GPU)")
@@ -538,6 +587,13 @@ def main():
         allc = [None] * world
         dist.all_gather_object(allc, comm[0])
         comm = allc
+    dumped = None
+    if args.dump_outputs:
+        # the state the last timed step left (before any further step below);
+        # N > 1: every rank writes the cells it owns
+        dumped = dump_outputs(solver, args.dump_outputs, f"_rank{rank}" if world > 1 else "",
+                              DUMP_MAX_CELLS // world)
+        log(f"[rank {rank}] outputs written to {args.dump_outputs}: {dumped}")
     comm_line = None
     timing = None
     if len(comm) > 1:
@@ -690,6 +746,8 @@ def main():
         },
         "linear_iterations_last_step": int(info.total_linear_iterations),
     }
+    if dumped:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "dtype": "float64"}
     st = load_step_traffic(args.round, args.config, world if not inproc else args.inproc_ranks)
     if st:
         gbs = st["bytes_per_step"] / (ms_per_step / 1e3) / 1e9
@@ -699,13 +757,15 @@ def main():
             "frac": gbs / HBM_PEAK_GBS,
             "source": st["source"] + " (committed PMC passes over one whole step; rate = those bytes / this run's step time)",
         }
-    if rank == 0 and world == 1 and not inproc and mesh is not None and args.outer > 0 and not args.no_cpu_baseline:
+    # runs of their own, beside the line's figures: only under --full
+    if (args.full and rank == 0 and world == 1 and not inproc and mesh is not None and args.outer > 0
+            and not args.no_cpu_baseline):
         try:
             out["cpu_baseline"] = cpu_baseline(mesh, n_cells, args.outer, args.inner, step_bytes, step_layout)
         except Exception as e:  # the baseline is reported, never the target
             log("cpu baseline failed:", e)
             out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not inproc and args.ref_workloads:
+    if args.full and rank == 0 and world == 1 and not inproc and args.ref_workloads:
         try:
             out["reference_workloads"] = reference_workloads()
         except Exception as e:

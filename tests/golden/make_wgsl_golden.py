@@ -22,6 +22,7 @@ oracle's canonical mode, flags 0).
 Run:  python -m tests.golden.make_wgsl_golden        (≈ 20 min)
       python -m tests.golden.make_wgsl_golden --only=C   (one mode, the rest kept)
       python -m tests.golden.make_wgsl_golden --c1   (BASELINE configs[1]: wgsl_ref_c1.npz)
+      python -m tests.golden.make_wgsl_golden --live (the one-step case of every mode: wgsl_ref_live.npz)
 """
 import hashlib
 import os
@@ -183,6 +184,36 @@ def main_c1():
     np.savez_compressed(os.path.join(HERE, "wgsl_ref_c1.npz"), **{f"{name}/B/{k}": v for k, v in res.items()})
 
 
+def live_setup(s, mesh):
+    from tests.test_oracle import setup_amg_test
+    setup_amg_test(s, mesh, 1)
+
+
+def live_mesh():
+    from tests.meshes import backwards_step
+    return backwards_step()
+
+
+# tests/test_wgsl_pin.py::test_live_reference_kernels: 1 step of 2 Picard x 4
+# FGMRES (AMG, amg_test setup) in every mode, recorded in wgsl_ref_live.npz so
+# that the test also runs where the reference's shaders cannot be read
+LIVE = ("live", live_mesh, live_setup, dict(convergence_lag=0, fixed_outer=2, fixed_inner=4), 1)
+
+
+def main_live():
+    from tests import wgsl_ref
+    if not wgsl_ref.available():
+        raise SystemExit("the reference's shader source is not readable: fixtures cannot be regenerated here")
+    name, mk, setup, kw, steps = LIVE
+    out = {}
+    for mode in "ABC":
+        res = run_wgsl(name, mk, setup, kw, steps, mode)
+        for k in ("digests", "info"):
+            out[f"{name}/{mode}/{k}"] = res[k]
+        print(f"{name} {mode}: info {res['info'][-1].tolist()}", flush=True)
+    np.savez_compressed(os.path.join(HERE, "wgsl_ref_live.npz"), **out)
+
+
 def main(only=None):
     """only: regenerate just these modes, keeping the file's other arrays"""
     from tests import wgsl_ref
@@ -213,5 +244,7 @@ def main(only=None):
 if __name__ == "__main__":
     if "--c1" in sys.argv:
         main_c1()
+    elif "--live" in sys.argv:
+        main_live()
     else:
         main(only=[a[len("--only="):] for a in sys.argv if a.startswith("--only=")] or None)

@@ -63,3 +63,32 @@ def test_bench_refuses_gpus_world_mismatch_before_gpu():
     r = subprocess.run([sys.executable, bench.__file__, "--gpus", "3"], env=env, capture_output=True, text=True,
                        timeout=60)
     assert r.returncode == 2 and "WORLD_SIZE=2" in r.stderr and r.stdout == ""
+
+
+def test_dump_cells_whole_below_the_limit_fixed_sample_above():
+    import numpy as np
+    assert bench.dump_cells(1000, max_cells=1000) is None
+    a = bench.dump_cells(1001, max_cells=1000)
+    assert a.shape == (1000,) and np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 1001
+    assert np.array_equal(a, bench.dump_cells(1001, max_cells=1000))  # the same cells in every run
+    # u (2 x f64) + p (f64) of the cells dumped stay under 64 MB
+    assert bench.DUMP_MAX_CELLS * 3 * 8 < 64e6
+
+
+def test_dump_outputs_writes_what_a_caller_reads(tmp_path):
+    import numpy as np
+
+    class Solver:
+        def get_u(self): return np.arange(14.0).reshape(7, 2)
+        def get_p(self): return np.arange(7.0) * 0.5
+
+    w = bench.dump_outputs(Solver(), str(tmp_path / "o"))
+    assert w == {"u": [7, 2], "p": [7]}
+    assert np.array_equal(np.load(tmp_path / "o" / "u.npy"), Solver().get_u())
+    assert np.array_equal(np.load(tmp_path / "o" / "p.npy"), Solver().get_p())
+    w = bench.dump_outputs(Solver(), str(tmp_path / "s"), "_rank1", max_cells=3)
+    sel = bench.dump_cells(7, 3)
+    assert w == {"u_rank1": [3, 2], "p_rank1": [3]}
+    u = np.load(tmp_path / "s" / "u_rank1.npy")
+    assert u.dtype == np.float64 and np.array_equal(u, Solver().get_u()[sel])
+    assert np.array_equal(np.load(tmp_path / "s" / "p_rank1.npy"), Solver().get_p()[sel])

@@ -1,5 +1,7 @@
 """bench.py keeps the driver's contract: one JSON line with the metric, the
-roofline and (N = 1) the CPU baseline objects (C1 workload, 1 timed step)."""
+roofline and (N = 1, --full) the CPU baseline objects (C1 workload, 1 timed
+step); a plain run times its steps alone and --dump-outputs writes what the
+last one computed."""
 import json
 import os
 import subprocess
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "1",
-                        "--warmup", "1", "--outer", "2", "--inner", "6"],
+                        "--warmup", "1", "--outer", "2", "--inner", "6", "--full"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -37,6 +39,43 @@ def test_bench_json_contract():
     assert g["reference_format_gbs"] > 0 and g["layout_true_gbs"] > 0
     assert abs(g["reference_format_gbs"] - d["step_reference_format_bytes_count"] / g["seconds_per_step"] / 1e9) \
         <= 1e-9 * g["reference_format_gbs"]
+    assert d["reference_workloads"]["solver_step"]["steps_timed"] >= 1
+
+
+def _plain_c0(tmp_path, name):
+    out = tmp_path / name
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c0",
+                        "--steps", "3", "--warmup", "1", "--outer", "2", "--inner", "6",
+                        "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), out
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line holds the headline figures and none of the runs
+    of their own; --dump-outputs writes the velocity and the pressure of every
+    cell after the last timed step, the same from run to run (C0: ~10 k cells,
+    3 timed steps of 2 Picard x 6 FGMRES iterations)."""
+    import numpy as np
+    d, out = _plain_c0(tmp_path, "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert "cpu_baseline" not in d and "reference_workloads" not in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    cells = d["config"]["cells_total"]
+    assert abs(d["value"] - cells / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    assert sorted(os.listdir(out)) == ["p.npy", "u.npy"]
+    u, p = np.load(out / "u.npy"), np.load(out / "p.npy")
+    assert u.dtype == np.float64 and p.dtype == np.float64
+    assert u.shape == (cells, 2) and p.shape == (cells,)
+    assert np.all(np.isfinite(u)) and np.all(np.isfinite(p))
+    assert np.abs(u).max() > 0 and np.abs(p).max() > 0  # the ramped inlet has moved the fluid
+    d2, out2 = _plain_c0(tmp_path, "b")
+    # the step is deterministic (DESIGN section 2): the same arguments give the same arrays
+    assert np.array_equal(np.load(out2 / "u.npy"), u) and np.array_equal(np.load(out2 / "p.npy"), p)
 
 
 def test_bench_two_process_launch_contract():

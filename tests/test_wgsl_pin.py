@@ -123,34 +123,43 @@ def test_kernels_canonical_equal_reference(fix, scheme, time_scheme):
 
 def test_fixture_holds_no_reference_text():
     """the fixture is data: numeric arrays and hex digests only"""
-    with np.load(FIX) as z:
-        for k in z.files:
-            a = z[k]
-            assert a.dtype.kind in "fiu" or (a.dtype.kind == "U" and all(len(s) == 64 for s in a.reshape(-1))), k
+    for path in (FIX, os.path.join(os.path.dirname(FIX), "wgsl_ref_live.npz")):
+        with np.load(path) as z:
+            for k in z.files:
+                a = z[k]
+                assert a.dtype.kind in "fiu" or (a.dtype.kind == "U" and all(len(s) == 64 for s in a.reshape(-1))), k
 
 
 # ------------------------------------------------------------------ live
 from tests import wgsl_ref  # noqa: E402
 
 
-@pytest.mark.skipif(not wgsl_ref.available(), reason="/root/reference is present only in the build container")
+FIX_LIVE = os.path.join(os.path.dirname(__file__), "golden", "wgsl_ref_live.npz")
+
+
 @pytest.mark.parametrize("mode", ["A", "B", "C"])
 def test_live_reference_kernels(mode):
-    """re-runs the reference shaders now (1 step of 2 Picard x 4 FGMRES, AMG,
-    amg_test setup) against the oracle in the matching semantics"""
-    from tests.meshes import backwards_step
-    from tests.test_oracle import setup_amg_test
-    mesh = backwards_step()
-    kw = dict(convergence_lag=0, fixed_outer=2, fixed_inner=4)
+    """the reference shaders' run of 1 step of 2 Picard x 4 FGMRES (AMG,
+    amg_test setup) against the oracle in the matching semantics: the run
+    recorded in tests/golden/wgsl_ref_live.npz (make_wgsl_golden.py --live)
+    everywhere, and the shaders re-run now where their source can be read"""
+    from tests.golden.make_wgsl_golden import LIVE
+    name, mk, setup, kw, _ = LIVE
+    mesh = mk()
     sched, bounds, flags, amg = MODES[mode]
-    r = wgsl_ref.WgslRefSolver(mesh, schedule=sched, bounds=bounds, amg=amg, **kw)
     o = OracleSolver(mesh, config=default_config(**kw))
     o.set_semantics(flags)
-    for s in (r, o):
-        setup_amg_test(s, mesh, 1)
-        s.step()
-    assert digest(r) == digest(o)
-    np.testing.assert_array_equal(info_vec(r), info_vec(o))
+    setup(o, mesh)
+    o.step()
+    with np.load(FIX_LIVE) as z:
+        assert digest(o) == str(z[f"{name}/{mode}/digests"][0])
+        np.testing.assert_array_equal(info_vec(o), z[f"{name}/{mode}/info"][0])
+    if wgsl_ref.available():
+        r = wgsl_ref.WgslRefSolver(mesh, schedule=sched, bounds=bounds, amg=amg, **kw)
+        setup(r, mesh)
+        r.step()
+        assert digest(r) == digest(o)
+        np.testing.assert_array_equal(info_vec(r), info_vec(o))
 
 
 # ------------------------------------------------------- the executor itself
