@@ -2471,12 +2471,12 @@ double Solver::layout_step_bytes() const {
       vc += (i == 0 ? smooth : (presmoothed ? 0.0 : 12 * n));
       if (d.rr_agg && !levels[i].dist)
         vc += 4 * nc + 4 * n + 2 * st + img + 14 * n + 12 * nc;       // fused residual + restriction
+      else
+        vc += (2 * st + img + 16 * n) + (16 * nc + 4 * n + 12 * nc);  // residual, restriction
       if (i > 0 && (size_t)i <= rr_pair.size() && rr_pair[i - 1].nblocks)
         vc -= 8 * n;  // second level of a k_amg_resrestrict_pair: its b and x stay in LDS
       if ((size_t)i < up_pair.size() && up_pair[i].nblocks)
         vc -= 8 * n;  // coarse level of a k_amg_prolong_smooth_pair: its smoothed x stays in LDS
-      else
-        vc += (2 * st + img + 16 * n) + (16 * nc + 4 * n + 12 * nc);  // residual, restriction
       if (fused_prolong(i))
         vc += smooth + 4 * n + 4 * nc;                                 // post-smoother reading x + P xc
       else

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from cfd2_amd import GpuSolver, default_config
+from tests.fv_checks import _coupled_csr, _scalar_csr_fast  # noqa: F401
 from tests.meshes import backwards_step, bench_mesh, channel_obstacle
 from tests.oracle_py import OracleSolver
 
@@ -276,40 +277,10 @@ def test_c1_scale_parity_and_true_residual():
     x = g.debug_buffer(4).astype(np.float64)
     vals = g.debug_buffer(9).astype(np.float64)
     A = _coupled_csr(mesh, vals)
-    r = np.linalg.norm(rhs - A @ x)
-    assert np.isfinite(r) and r <= 1e-3 * np.linalg.norm(rhs) + 2 * ig.residual, (r, ig.residual)
-
-
-def _coupled_csr(mesh, vals):
-    """Reference coupled CSR (init/linear_solver/mod.rs:180-216) as scipy from the
-    scalar pattern: block row i holds sub-rows u, v, p, each listing
-    (3j, 3j+1, 3j+2) for the neighbours j of i in ascending order."""
-    import scipy.sparse as sp
-    srow, scol = _scalar_csr_fast(mesh)
-    n = len(srow) - 1
-    deg = np.diff(srow)
-    base3 = (3 * scol[:, None] + np.arange(3)[None, :]).reshape(-1)
-    pos = np.arange(9 * len(scol))
-    row = np.repeat(np.arange(n), 9 * deg)
-    off = pos - 9 * srow[row]
-    sub = off // (3 * deg[row])
-    cols = base3[3 * srow[row] + off % (3 * deg[row])]
-    return sp.csr_matrix((vals, (3 * row + sub, cols)), shape=(3 * n, 3 * n))
-
-
-def _scalar_csr_fast(mesh):
-    a = mesh.arrays()
-    n = len(a["cell_cx"])
-    own = a["face_owner"].astype(np.int64)
-    nb = a["face_neighbor"].astype(np.int64)
-    m = nb != 0xFFFFFFFF
-    r = np.concatenate([np.arange(n), own[m], nb[m]])
-    c = np.concatenate([np.arange(n), nb[m], own[m]])
-    key = np.unique(r * n + c)
-    rr, cc = key // n, key % n
-    srow = np.zeros(n + 1, dtype=np.int64)
-    np.add.at(srow, rr + 1, 1)
-    return np.cumsum(srow), cc
+    assert A.shape == (3 * mesh.num_cells(),) * 2 and len(rhs) == len(x) == A.shape[0]
+    from tests import fv_cases, fv_checks
+    # fixed 1 x 6 schedule: the report is a computed b - A x, the bound purely relative
+    fv_checks.check_residual(fv_checks.System(mesh, g), ig.residual, fv_cases.RESIDUAL_TOL, 0.0, "C1 scale")
 
 
 def test_reproduce_divergence_gpu():
@@ -681,3 +652,57 @@ def test_amg_resrestrict_pair_parity(mesh_name, pair, monkeypatch, capfd):
         pairs = [] if m.group(grp).strip() == "none" else m.group(grp).split()
         assert (len(pairs) > 0) == (pair == "2"), (grp, pairs)
     g.close()
+
+
+def _layout_bytes(mesh, monkeypatch, capfd, **env):
+    """step_layout_bytes / step_algorithmic_bytes / AMG levels / paired levels
+    of a 2 x 8 fixed schedule after one step (the hierarchy is built by the
+    first solve), with the tail off as test_amg_resrestrict_pair_parity sets it."""
+    import re
+    for k in ("CFD_AMG_FUSED_RR_ROWS", "CFD_AMG_FUSED_PAIR"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("CFD_AMG_TAIL_ROWS", "0")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    g = GpuSolver(mesh, config=default_config(log_level=2, fixed_outer=2, fixed_inner=8))
+    _setup_amg_test(g, mesh, 1)
+    capfd.readouterr()
+    g.step()
+    m = re.search(r"down-leg pairs:(.*), up-leg pairs:(.*)\n", capfd.readouterr().err)
+    assert m, "no AMG setup line"
+    down, up = ([] if m.group(i).strip() == "none" else [tuple(int(x) for x in p.split("+")) for p in m.group(i).split()]
+                for i in (1, 2))
+    out = (g.step_layout_bytes(), g.step_algorithmic_bytes(), g.amg_levels(), down, up)
+    g.close()
+    return out
+
+
+@pytest.mark.parametrize("mesh_name", ["amg_test", "graded", "channel_012"])
+def test_layout_step_bytes_fused_and_paired(mesh_name, monkeypatch, capfd):
+    """cfd_step_layout_bytes (bench.py's step_layout_bytes / layout_true_gbs)
+    counts a level's residual + restriction once: the fused cost where the
+    level runs k_amg_resrestrict, the two kernels' cost elsewhere.  No byte
+    model is restated here: (a) with no level fused the count is strictly
+    larger than with the default fusion; (b) pairing changes it by exactly
+    8 n bytes per paired level (the b and x, or the smoothed x, that stay in
+    LDS) per V-cycle; (c) it stays below the reference-format count."""
+    if mesh_name == "amg_test":
+        mesh = backwards_step()
+    elif mesh_name == "graded":
+        from cfd2_amd.mesh import ChannelWithObstacle, generate_cut_cell_mesh
+        geo = ChannelWithObstacle(length=3.0, height=1.0, obstacle_center=(1.0, 0.5), obstacle_radius=0.15)
+        mesh = generate_cut_cell_mesh(geo, 0.02, 0.08, 1.2, (3.0, 1.0))
+    else:
+        mesh = channel_obstacle(h=0.012)
+    fused, algo, levels, _, _ = _layout_bytes(mesh, monkeypatch, capfd, CFD_AMG_FUSED_PAIR="0")
+    unfused, _, levels_u, down_u, up_u = _layout_bytes(mesh, monkeypatch, capfd, CFD_AMG_FUSED_PAIR="0",
+                                                      CFD_AMG_FUSED_RR_ROWS="0")
+    assert levels_u == levels and len(levels) >= 2 and not down_u and not up_u
+    assert unfused > fused, (unfused, fused)  # (a)
+    paired, _, levels_p, down, up = _layout_bytes(mesh, monkeypatch, capfd, CFD_AMG_FUSED_PAIR="2")
+    assert levels_p == levels and down and up
+    vcycles = 2 * 8  # fixed_outer x fixed_inner, one V-cycle per FGMRES iteration
+    kept = sum(levels[b][0] for _, b in down) + sum(levels[a][0] for a, _ in up)  # rows whose vectors stay in LDS
+    assert fused - paired == 8.0 * kept * vcycles, (fused, paired, down, up, levels)  # (b)
+    for v in (fused, unfused, paired):
+        assert 0.0 < v < algo, (v, algo)  # (c)
