@@ -878,7 +878,11 @@ void Solver::refresh_amg() {
     }
   }
   CFD_HIP(hipGetLastError());
-  if (tail_blob_first >= 0) build_tail_blob(tail_blob_first, true);
+  if (tail_blob_first >= 0) {  // the kept schedule (vc_plan) names the LDS image: it has to stay one
+    const int tf = tail_blob_first;
+    build_tail_blob(tf, true);
+    if (tail_blob_first != tf) throw std::logic_error("AMG refresh: tail blob layout changed");
+  }
   sync();
 }
 

@@ -323,4 +323,55 @@ bool build_up_pair_partition(const std::vector<uint32_t>& frow, const std::vecto
   return true;
 }
 
+// amg.rs:666-770 with this library's fused forms.  Replicated levels from
+// tail_first on run as one single-workgroup kernel; the levels above it go
+// down (pre-smooth, residual, restriction) and up (prolongation, post-smooth).
+std::vector<VcOp> plan_v_cycle(const std::vector<VcLevel>& lv, int tail_first, bool tail_lds_image) {
+  const int L = (int)lv.size();
+  // the tail needs level >= 1 (level 0's x / b are bound per call)
+  if (L < 1 || tail_first < 1 || tail_first > L) throw std::invalid_argument("V-cycle plan: tail_first outside [1, L]");
+  const int down = v_cycle_down(tail_first, L);
+  std::vector<VcOp> ops;
+  bool pre = false;  // the level's zero-x pre-smoother ran inside the restriction into it
+  for (int i = 0; i < down;) {
+    if (pre)
+      ops.push_back({VcKind::TakePreSmoothed, i, false});
+    else
+      ops.push_back({VcKind::PreSmooth, i, i > 0});  // coarse x was cleared by the restriction (ghosts too)
+    // the next level is pre-smoothed on this leg: its zero-x sweep is fused into the restriction
+    pre = i + 1 < down && (!lv[i].dist || lv[i + 1].dist);
+    if (pre && lv[i].down_pair && i + 2 <= down) {
+      // levels i and i + 1 in one launch; level i + 1 ends pre-smoothed and level i + 2 gets its rhs
+      pre = i + 2 < down;  // both replicated / single-GPU
+      ops.push_back({VcKind::ResRestrictPair, i, pre});
+      i += 2;
+      continue;
+    }
+    ops.push_back({!lv[i].dist && lv[i].fused_rr ? VcKind::ResRestrictFused : VcKind::ResidualRestrict, i, pre});
+    if (lv[i].dist && !lv[i + 1].dist) ops.push_back({VcKind::GatherRhs, i + 1, false});
+    ++i;
+  }
+  if (tail_first < L)
+    ops.push_back({tail_lds_image ? VcKind::TailBlob : VcKind::Tail, tail_first, false});
+  else
+    ops.push_back({VcKind::CoarsestSweeps, L - 1, false});
+  for (int i = down - 1; i >= 0;) {
+    // a row-partitioned coarse level: the prolongation reads ghosts of its x, no fused form
+    const bool plain = lv[i + 1].dist;
+    if (!plain && i >= 1 && lv[i].up_pair) {
+      ops.push_back({VcKind::ProlongSmoothPair, i, false});
+      i -= 2;
+      continue;
+    }
+    if (!plain && lv[i].fused_prolong) {
+      ops.push_back({VcKind::PostSmoothProlong, i, false});
+    } else {
+      ops.push_back({VcKind::Prolong, i, false});
+      ops.push_back({VcKind::PostSmooth, i, false});
+    }
+    --i;
+  }
+  return ops;
+}
+
 }  // namespace cfd2

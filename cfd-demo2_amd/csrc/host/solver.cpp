@@ -1,7 +1,7 @@
 // Host driver of the HIP coupled step: restates the control flow of
 //   coupled_solver.rs:33-580            step_coupled / check_evolution
 //   coupled_solver_fgmres.rs:1728-2448  solve_coupled_fgmres (FGMRES(50) + Schur)
-//   linear_solver/amg.rs:666-770        v_cycle
+//   linear_solver/amg.rs:666-770        v_cycle (amg_cycle.cpp)
 //   solver.rs:9-44, 97-128, 276-294     set_u / set_p / set_dt / getters / history
 // over the kernels of ../hip/kernels.hip, on one HIP stream.  All vectors stay
 // in HBM; host round trips are the ones the reference control flow needs
@@ -950,6 +950,7 @@ void Solver::drop_amg() {
   amg_refresh.clear();
   rr_pair.clear();  // their block images lived in amg_arena
   up_pair.clear();
+  vc_plan.clear();
   amg_setup_flag = nullptr;
   amg_refresh_pending = false;
   amg_arena.release();
@@ -1004,597 +1005,24 @@ void Solver::ensure_amg() {
     arena.release();  // the device attempt's partial hierarchy
     build_amg_host();
   }
-  const int L = (int)levels.size();
-  set_resrestrict_blocks();
-  // post-smoothers with the prolongation fused (single-GPU / replicated
-  // levels of at most CFD_AMG_FUSED_PROLONG_ROWS rows; 0: never)
-  fuse_prolong_rows = knob_u64(Knob::AmgFusedProlongRows, 1ull << 20);
-  // the tail form: blob<K> (default blob2), lds, global
-  {
-    const char* tf = knob(Knob::AmgTail);
-    tail_form = 2;
-    tail_blob_shift = 2;
-    if (tf && std::strncmp(tf, "blob", 4) == 0) {
-      if (tf[4]) tail_blob_shift = std::max(0, (int)std::strtol(tf + 4, nullptr, 10));
-    } else if (tf && std::strcmp(tf, "lds") == 0) {
-      tail_form = 1;
-    } else if (tf && std::strcmp(tf, "global") == 0) {
-      tail_form = 0;
-    } else if (tf) {
-      throw std::invalid_argument(std::string("CFD_AMG_TAIL: expected blob<K>, lds or global, got ") + tf);
-    }
-  }
-  // replicated levels from `tail_first` down run inside one single-workgroup kernel
-  const uint32_t tail_rows = (uint32_t)knob_u64(Knob::AmgTailRows, 4096u);
-  const int lo = std::max(amg_g, 1);
-  tail_first = L;
-  while (tail_first > lo && levels[tail_first - 1].dev.n <= tail_rows) --tail_first;
-  // wide levels (16-bit row lengths) run only in the one-workgroup tail kernels
-  {
-    int bad = -1;  // first wide level the row kernels would run (level 0 or a row-partitioned level)
-    for (int li = 0; li < L; ++li)
-      if (levels[li].wide) {
-        if (li < lo)
-          bad = li;
-        else
-          tail_first = std::min(tail_first, li);
-        break;
-      }
-    // the width of a row-partitioned level is per rank: every rank throws together
-    uint64_t any_bad = bad >= 0 ? 1 : 0;
-    if (dist())
-      for (uint64_t f : allgather_u64(any_bad)) any_bad |= f;
-    if (any_bad)
-      throw std::invalid_argument("AMG: rows wider than 255 entries on a level the row kernels run (level 0 or a "
-                                  "row-partitioned level): unsupported layout");
-  }
-  std::vector<AmgTailLevel> tl(L);
-  for (int li = 0; li < L; ++li) {
-    tl[li].L = levels[li].dev;
-    tl[li].x = levels[li].x;
-    tl[li].xt = levels[li].xt;
-    tl[li].b = levels[li].b;
-    tl[li].r = levels[li].r;
-  }
-  d_tail = arena.upload(tl, stream);
-  check_launch("AMG setup");
-  if (tail_form == 2) {
-    // The LDS image of the tail (matrices included) is the fast tail; when it
-    // does not fit in one CU's LDS, up to tail_blob_shift (CFD_AMG_TAIL=blob<K>,
-    // default 2) more levels run with the row kernels so that it does (C1: the
-    // 3.9 k-row level).
-    const int shift = tail_blob_shift;
-    const int t0 = std::max({tail_first, 1, dist() ? amg_g : 0});
-    for (int t = t0; t < std::min(L, t0 + 1 + shift) && tail_blob_first < 0; ++t) {
-      if (t > t0 && levels[t - 1].wide) break;  // wide levels run only in the tail kernels
-      build_tail_blob(t);
-      if (tail_blob_first >= 0) tail_first = t;
-    }
-  }
-  build_rr_pairs();
+  finish_amg_schedule();
   sync();
   amg_built = true;
   if (!from_checkpoint) amg_age = 0;
   if (timing) {
-    std::string pairs;
-    for (int li = 0; li < (int)rr_pair.size(); ++li)
-      if (rr_pair[li].nblocks) pairs += " " + std::to_string(li) + "+" + std::to_string(li + 1);
-    std::string ups;
-    for (int li = 0; li < (int)up_pair.size(); ++li)
-      if (up_pair[li].nblocks) ups += " " + std::to_string(li) + "+" + std::to_string(li - 1);
+    std::string pairs, ups;  // the pairs the schedule runs, either leg by ascending level
+    for (const VcOp& op : vc_plan) {
+      const std::string a = " " + std::to_string(op.level) + "+";
+      if (op.kind == VcKind::ResRestrictPair) pairs += a + std::to_string(op.level + 1);
+      if (op.kind == VcKind::ProlongSmoothPair) ups = a + std::to_string(op.level - 1) + ups;
+    }
     std::fprintf(stderr,
                  "[amg setup] %s path: %d levels in %.3f s, tail from level %d (LDS image from level %d), "
                  "down-leg pairs:%s, up-leg pairs:%s\n",
-                 how, L, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(),
-                 tail_first, tail_blob_first, pairs.empty() ? " none" : pairs.c_str(), ups.empty() ? " none" : ups.c_str());
+                 how, (int)levels.size(),
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), tail_first,
+                 tail_blob_first, pairs.empty() ? " none" : pairs.c_str(), ups.empty() ? " none" : ups.c_str());
   }
-}
-
-// Aggregates per block of k_amg_resrestrict for the single-GPU / replicated
-// levels with a coarse level and at most CFD_AMG_FUSED_RR_ROWS rows (default
-// 2^18; distributed levels restrict ghost residuals and keep the two
-// kernels): about 256 members per block, fewer aggregates while a block's
-// members exceed its LDS capacity.  Its one-row-per-thread residual over
-// permuted rows only pays on the latency-bound levels: same-box A/B
-// (profiles/r03/ab_log.md) C2 level 0 129 vs 68 + 34 us, level 1 104 vs
-// 56 + 13 us; C1 levels of 125 k rows and fewer 6-8 vs 10-11 us.
-// CFD_AMG_FUSED_RR_ROWS=0 keeps the two kernels everywhere.
-void Solver::set_resrestrict_blocks() {
-  const uint64_t max_rows = knob_u64(Knob::AmgFusedRrRows, 1u << 18);
-  for (AmgGpuLevel& G : levels) {
-    AmgLevelDev& d = G.dev;
-    d.rr_agg = 0;
-    if (max_rows == 0 || G.dist || d.nc == 0 || d.n == 0 || d.n > max_rows || !d.r_row) continue;
-    std::vector<uint32_t> rr((size_t)d.nc + 1);
-    CFD_HIP(hipMemcpyAsync(rr.data(), d.r_row, rr.size() * 4, hipMemcpyDeviceToHost, stream));
-    sync();
-    uint32_t a = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(256, (uint64_t)256 * d.nc / d.n));
-    for (; a >= 1; a /= 2) {
-      uint32_t worst = 0;
-      for (uint32_t I = 0; I < d.nc; I += a) worst = std::max(worst, rr[std::min(I + a, d.nc)] - rr[I]);
-      if (worst <= kRRCap) break;
-    }
-    d.rr_agg = a;
-  }
-}
-
-// Down-leg pairs (k_amg_resrestrict_pair): greedily from the top, two
-// adjacent levels that both take k_amg_resrestrict and whose second level is
-// pre-smoothed inside the V-cycle's down loop run as one launch.
-void Solver::build_rr_pairs() {
-  const int L = (int)levels.size();
-  rr_pair.assign(L, AmgPairImage{});
-  up_pair.assign(L, AmgUpPairImage{});
-  pair_mode = (int)knob_u64(Knob::AmgFusedPair, 1);  // 0 off, 1 where cheap, 2 every candidate (tests)
-  if (pair_mode == 0) return;
-  const int D = dist() ? amg_g : 0;
-  const int down = std::min(std::max({tail_first, 1, D}), L - 1);
-  for (int i = 0; i + 1 < down;) {
-    const AmgGpuLevel &F = levels[i], &M = levels[i + 1];
-    const bool ok = !F.dist && !M.dist && !F.wide && !M.wide && F.dev.rr_agg && M.dev.rr_agg && M.dev.w >= 1;
-    i += (ok && build_rr_pair(i)) ? 2 : 1;
-  }
-  // up-leg: from the bottom, post-smoothers of levels c and c - 1 that both
-  // take the fused prolongation, fine level at most 2^18 rows
-  for (int c = down - 1; c >= 1;) {
-    const AmgGpuLevel &C = levels[c], &F = levels[c - 1];
-    const bool ok = fused_prolong(c) && fused_prolong(c - 1) && !C.wide && !F.wide && F.dev.n <= (1u << 18) &&
-                    F.dev.w >= 1 && C.dev.agg;
-    c -= (ok && build_up_pair(c)) ? 2 : 1;
-  }
-}
-
-// The up-leg pair image of levels (c, c - 1): blocks of kUpPairRows fine rows
-// and the level-c rows T they need (kUpPairCap at most), with the T-local
-// index of every fine slot's column aggregate.  Mode 1 pairs only while the
-// blocks' T rows total at most 2.5x the level's rows (profiles/r06/ab_log.md,
-// C1: levels 5+4 9.1 us against 7.5 + 6.3, in; 3+2 13.1 against 6.8 + 6.7,
-// out).
-bool Solver::build_up_pair(int c) {
-  const AmgLevelDev &F = levels[c - 1].dev, &C = levels[c].dev;
-  const uint32_t nf = F.n;
-  const size_t slots = (size_t)F.w * F.stride;
-  std::vector<uint8_t> flen(nf);
-  std::vector<uint32_t> agg(nf);
-  std::vector<int32_t> fc(slots);
-  CFD_HIP(hipMemcpyAsync(flen.data(), F.len, nf, hipMemcpyDeviceToHost, stream));
-  CFD_HIP(hipMemcpyAsync(agg.data(), F.agg, (size_t)nf * 4, hipMemcpyDeviceToHost, stream));
-  if (F.use16) {
-    std::vector<int16_t> c16(slots);
-    CFD_HIP(hipMemcpyAsync(c16.data(), F.col16, slots * 2, hipMemcpyDeviceToHost, stream));
-    sync();
-    for (size_t k = 0; k < slots; ++k) fc[k] = (int32_t)(k % F.stride) + c16[k];
-  } else {
-    CFD_HIP(hipMemcpyAsync(fc.data(), F.col32, slots * 4, hipMemcpyDeviceToHost, stream));
-    sync();
-  }
-  std::vector<uint32_t> frow(nf + 1, 0), fcol;
-  for (uint32_t g = 0; g < nf; ++g) frow[g + 1] = frow[g] + flen[g];
-  fcol.resize(frow[nf]);
-  for (uint32_t g = 0; g < nf; ++g)
-    for (uint32_t r = 0; r < flen[g]; ++r) fcol[frow[g] + r] = (uint32_t)fc[(size_t)r * F.stride + g];
-  UpPairPartition up;
-  if (!build_up_pair_partition(frow, fcol, agg, C.n, kUpPairRows, kUpPairCap, up)) return false;
-  if (pair_mode < 2 && (double)up.t.size() > 2.5 * (double)C.n) return false;
-  std::vector<uint16_t> lt(slots, 0), lto(F.stride, 0);
-  for (uint32_t g = 0; g < nf; ++g) {
-    lto[g] = up.lto[g];
-    for (uint32_t r = 0; r < flen[g]; ++r) lt[(size_t)r * F.stride + g] = up.lt[frow[g] + r];
-  }
-  AmgUpPairImage& P = up_pair[c];
-  P.nblocks = (uint32_t)up.tb.size() - 1;
-  P.tb = arena.upload(up.tb, stream);
-  P.t = arena.upload(up.t, stream);
-  P.lt = arena.upload(lt, stream);
-  P.lto = arena.upload(lto, stream);
-  sync();
-  return true;
-}
-
-// The pair image of levels (i, i+1): blocks of level-(i+2) aggregates whose
-// level-(i+1) rows (members + ring: S) and level-i members of S each fit
-// kPairThreads.  False (no pair) when one aggregate alone does not fit.
-bool Solver::build_rr_pair(int i) {
-  const AmgLevelDev &F = levels[i].dev, &M = levels[i + 1].dev;
-  const uint32_t nm = M.n, nc = M.nc;
-  auto down_u32 = [&](const uint32_t* d, size_t n) {
-    std::vector<uint32_t> h(n);
-    CFD_HIP(hipMemcpyAsync(h.data(), d, n * 4, hipMemcpyDeviceToHost, stream));
-    return h;
-  };
-  const std::vector<uint32_t> fr_row = down_u32(F.r_row, (size_t)F.nc + 1), fr_col = down_u32(F.r_col, F.n);
-  const std::vector<uint32_t> mr_row = down_u32(M.r_row, (size_t)nc + 1), mr_col = down_u32(M.r_col, nm);
-  std::vector<uint8_t> mlen(nm);
-  CFD_HIP(hipMemcpyAsync(mlen.data(), M.len, nm, hipMemcpyDeviceToHost, stream));
-  const size_t slots = (size_t)M.w * M.stride;
-  std::vector<int32_t> mcol(slots);
-  if (M.use16) {
-    std::vector<int16_t> c16(slots);
-    CFD_HIP(hipMemcpyAsync(c16.data(), M.col16, slots * 2, hipMemcpyDeviceToHost, stream));
-    sync();
-    for (size_t k = 0; k < slots; ++k) mcol[k] = (int32_t)(k % M.stride) + c16[k];
-  } else {
-    CFD_HIP(hipMemcpyAsync(mcol.data(), M.col32, slots * 4, hipMemcpyDeviceToHost, stream));
-    sync();
-  }
-  if (F.nc != nm) return false;
-  // the off-diagonal pattern of level i + 1 as CSR in slot order
-  std::vector<uint32_t> mrow(nm + 1, 0), mcsr;
-  for (uint32_t g = 0; g < nm; ++g) mrow[g + 1] = mrow[g] + mlen[g];
-  mcsr.resize(mrow[nm]);
-  for (uint32_t g = 0; g < nm; ++g)
-    for (uint32_t r = 0; r < mlen[g]; ++r) mcsr[mrow[g] + r] = (uint32_t)mcol[(size_t)r * M.stride + g];
-  // 256-thread blocks (one CU each, like the k_amg_resrestrict launches they
-  // replace) while the ring's redundant level-i rows stay within 50 %
-  // (profiles/r06/ab_log.md, C1: levels 4+5 at 1.41x rows 7.8 us against
-  // 5.5 + 5.1; levels 2+3 at 2.9x 16.1 us against 7.1 + 6.3; 1,024-thread
-  // blocks -- less redundancy, a quarter of the CUs -- lost on both pairs)
-  PairPartition pp;
-  const uint32_t threads = 256;
-  if (!build_pair_partition(fr_row, fr_col, mr_row, mr_col, mrow, mcsr, threads, pp)) return false;
-  if (pair_mode < 2 && (double)pp.f.size() > 1.5 * (double)F.n) return false;
-  std::vector<uint16_t> lc(slots, 0);
-  for (uint32_t g = 0; g < nm; ++g)
-    for (uint32_t r = 0; r < mlen[g]; ++r) lc[(size_t)r * M.stride + g] = pp.lc[mrow[g] + r];
-  const uint32_t nb = (uint32_t)pp.jb.size() - 1;
-  const std::vector<uint32_t>&jb = pp.jb, &sb = pp.sb, &sv = pp.s, &fo = pp.fo, &fv = pp.f;
-  AmgPairImage& P = rr_pair[i];
-  P.nblocks = nb;
-  P.threads = threads;
-  P.jb = arena.upload(jb, stream);
-  P.sb = arena.upload(sb, stream);
-  P.s = arena.upload(sv, stream);
-  P.fo = arena.upload(fo, stream);
-  P.f = arena.upload(fv, stream);
-  P.lc = arena.upload(lc, stream);
-  sync();
-  return true;
-}
-
-// LDS image of the tail levels [tf, L) for k_amg_tail_blob: every array the
-// tail V-cycle reads, compacted (off-diagonal CSR, u16 indices) from the
-// level images, when vectors + blob fit in one CU's LDS.
-void Solver::build_tail_blob(int tf, bool reuse) {
-  const uint32_t old_words = tail_blob_words;
-  tail_blob_first = -1;
-  const int L = (int)levels.size();
-  if (tf >= L) return;
-  std::vector<uint32_t> blob;
-  std::vector<TailBlobLevel> desc(L);
-  auto align4 = [&] {
-    while (blob.size() % 4) blob.push_back(0);
-    return (uint32_t)blob.size();
-  };
-  auto put_f = [&](const float* v, size_t n) {
-    const uint32_t o = align4();
-    for (size_t i = 0; i < n; ++i) {
-      uint32_t w;
-      std::memcpy(&w, v + i, 4);
-      blob.push_back(w);
-    }
-    return o;
-  };
-  auto put_u32 = [&](const std::vector<uint32_t>& v) {
-    const uint32_t o = align4();
-    blob.insert(blob.end(), v.begin(), v.end());
-    return o;
-  };
-  auto put_u16 = [&](const std::vector<uint32_t>& v) {
-    const uint32_t o = align4();
-    for (size_t i = 0; i < v.size(); i += 2)
-      blob.push_back((v[i] & 0xFFFFu) | ((i + 1 < v.size() ? v[i + 1] & 0xFFFFu : 0u) << 16));
-    return o;
-  };
-  auto put_u8 = [&](const std::vector<uint8_t>& v) {
-    const uint32_t o = align4();
-    for (size_t i = 0; i < v.size(); i += 4) {
-      uint32_t w = 0;
-      for (size_t b = 0; b < 4 && i + b < v.size(); ++b) w |= (uint32_t)v[i + b] << (8 * b);
-      blob.push_back(w);
-    }
-    return o;
-  };
-  auto d2h = [&](void* dst, const void* src, size_t bytes) {
-    if (bytes) CFD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-  };
-  uint32_t vec = 0;
-  for (int l = tf; l < L; ++l) {
-    const AmgLevelDev& d = levels[l].dev;
-    const uint32_t n = d.n, st = d.stride;
-    if (n > 65535 || d.nc > 65535 || levels[l].wide) return;  // the blob keeps u8 diagonal ranks
-    const size_t slots = (size_t)std::max(d.w, 1) * st;
-    std::vector<uint8_t> len(n), drank(n);
-    std::vector<float> dv(n), de(n), val(slots);
-    std::vector<int16_t> c16(d.use16 ? slots : 0);
-    std::vector<int32_t> c32(d.use16 ? 0 : slots);
-    d2h(len.data(), d.len, n);
-    d2h(drank.data(), d.drank, n);
-    d2h(dv.data(), d.dv, (size_t)n * 4);
-    d2h(de.data(), d.de, (size_t)n * 4);
-    d2h(val.data(), d.val, slots * 4);
-    if (d.use16) d2h(c16.data(), d.col16, slots * 2);
-    else d2h(c32.data(), d.col32, slots * 4);
-    std::vector<uint32_t> agg, rrow, rcol;
-    if (d.nc) {
-      agg.resize(n);
-      rrow.resize((size_t)d.nc + 1);
-      d2h(agg.data(), d.agg, (size_t)n * 4);
-      d2h(rrow.data(), d.r_row, rrow.size() * 4);
-    }
-    sync();
-    if (d.nc) {
-      rcol.resize(rrow[d.nc]);
-      d2h(rcol.data(), d.r_col, rcol.size() * 4);
-      sync();
-    }
-    std::vector<uint32_t> ro(n + 1, 0), cols;
-    std::vector<float> vals;
-    for (uint32_t i = 0; i < n; ++i) {
-      ro[i + 1] = ro[i] + len[i];
-      for (uint32_t r = 0; r < len[i]; ++r) {
-        const size_t o = (size_t)r * st + i;
-        const int64_t c = d.use16 ? (int64_t)i + c16[o] : (int64_t)c32[o];
-        if (c < 0 || c >= (int64_t)n) return;  // tail levels are replicated: global columns
-        cols.push_back((uint32_t)c);
-        vals.push_back(val[o]);
-      }
-    }
-    TailBlobLevel& D = desc[l];
-    D.n = n;
-    D.nc = d.nc;
-    D.maxlen = n ? *std::max_element(len.begin(), len.end()) : 0;
-    D.de = put_f(de.data(), n);
-    D.dv = put_f(dv.data(), n);
-    D.rowoff = put_u32(ro);
-    D.drank = put_u8(drank);
-    D.val = put_f(vals.data(), vals.size());
-    D.col = put_u16(cols);
-    if (d.nc) {
-      D.agg = put_u16(agg);
-      D.r_row = put_u16(rrow);
-      D.r_col = put_u16(rcol);
-    }
-    vec += 4 * ((n + 3) & ~3u);
-  }
-  align4();
-  if (4 * ((size_t)vec + blob.size()) > lds_budget) return;
-  if (reuse && d_tail_blob && blob.size() == old_words) {  // same structure: new values in place
-    CFD_HIP(hipMemcpyAsync(d_tail_blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, stream));
-    CFD_HIP(hipMemcpyAsync(d_tail_desc, desc.data(), desc.size() * sizeof(TailBlobLevel), hipMemcpyHostToDevice,
-                           stream));
-    sync();  // the host staging vectors die here
-  } else {
-    if (reuse) throw std::logic_error("AMG refresh: tail blob layout changed");
-    d_tail_blob = arena.upload(blob, stream);
-    d_tail_desc = arena.upload(desc, stream);
-  }
-  tail_blob_words = (uint32_t)blob.size();
-  tail_vec_floats = vec;
-  tail_blob_first = tf;
-}
-
-// Timing of level-0 smoother launches (bench roofline): a pair of pool events
-// per launch, recorded by the GPU at kernel start / end (hipExtLaunchKernel).
-// The pool is created before the timed steps (cfd_profile_reset) and grows
-// without synchronising; only at kProfPoolMax events is it drained (a stream
-// synchronisation) into prof_ms.
-std::pair<hipEvent_t, hipEvent_t> Solver::prof_pair() {
-  if (prof_used + 2 > prof_ev.size()) {
-    if (prof_ev.size() < kProfPoolMax) {
-      prof_grow(prof_ev.size() + 1024);  // no synchronisation inside the timed steps
-    } else {
-      CFD_HIP(hipStreamSynchronize(stream));
-      for (size_t k = 0; k + 1 < prof_used; k += 2) {
-        float ms = 0.0f;
-        CFD_HIP(hipEventElapsedTime(&ms, prof_ev[k], prof_ev[k + 1]));
-        prof_ms += ms;
-      }
-      prof_used = 0;
-    }
-  }
-  prof_used += 2;
-  return {prof_ev[prof_used - 2], prof_ev[prof_used - 1]};
-}
-
-void Solver::prof_grow(size_t n) {
-  while (prof_ev.size() < n) {
-    hipEvent_t e;
-    CFD_HIP(hipEventCreate(&e));
-    prof_ev.push_back(e);
-  }
-}
-
-void Solver::amg_smooth(size_t li, float*& xcur, const float* b, bool x_zero, bool nt) {
-  AmgGpuLevel& L = levels[li];
-  if (x_zero) {
-    launch_amg_smooth_zero(L.dev, b, L.xt, stream);
-  } else if (li == 0 && prof_take()) {
-    if (capturing) {  // event nodes of the graph around the launch, read per replay (graph_harvest)
-      hipEvent_t e0, e1;
-      CFD_HIP(hipEventCreate(&e0));
-      capturing->ev.push_back(e0);
-      CFD_HIP(hipEventCreate(&e1));
-      capturing->ev.push_back(e1);
-      CFD_HIP(hipEventRecordWithFlags(e0, stream, hipEventRecordExternal));
-      launch_amg_smooth(L.dev, xcur, b, L.xt, stream, nullptr, nullptr, nt);
-      CFD_HIP(hipEventRecordWithFlags(e1, stream, hipEventRecordExternal));
-    } else {
-      const auto ev = prof_pair();
-      launch_amg_smooth(L.dev, xcur, b, L.xt, stream, ev.first, ev.second, nt);
-      prof_launches++;
-    }
-  } else {
-    launch_amg_smooth(L.dev, xcur, b, L.xt, stream, nullptr, nullptr, nt);
-  }
-  std::swap(xcur, L.xt);  // out-of-place Jacobi: the partner buffer becomes current
-}
-
-// amg.rs:666-770, level 0 bound to (x = p_sol, b = temp_p).  Replicated levels
-// from `tail_first` on run as one single-workgroup kernel (k_amg_tail).  On a
-// distributed rank the levels below amg_g are row-partitioned: each smoother
-// input gets a halo (the cleared coarse x needs none), the restriction into
-// the first replicated level is all-gathered.
-void Solver::v_cycle() {
-  const int L = (int)levels.size();
-  levels[0].x = p_sol;
-  levels[0].b = temp_p;
-  if (ref_inplace || ref_clamp) {
-    v_cycle_reference();
-    return;
-  }
-  const int D = dist() ? amg_g : 0;
-  // the tail needs level >= 1 (level 0's x/b are bound per call) and is off
-  // while the level-0 smoother is being timed on a one-level hierarchy
-  const int tf = (prof && L == 1) ? L : std::max({tail_first, 1, D});
-  const int down = std::min(tf, L - 1);
-  // smoother sweep; on a distributed level the x halo overlaps the interior rows
-  // post: the up-sweep's smoother (nontemporal matrix loads with nt_mask bit 1)
-  auto sm = [&](int i, bool x_zero, bool post = false) {
-    AmgGpuLevel& Lv = levels[i];
-    const bool ntl = nt(post ? 1u : 16u);
-    if (!Lv.dist || x_zero) {
-      amg_smooth(i, Lv.x, Lv.b, x_zero, ntl);
-      return;
-    }
-    const bool timed = i == 0 && prof_take();  // kernel time only: each part timed separately
-    const CommScope cs(this, amg_cat(i));
-    overlapped(Lv.plan, {{Lv.x, 1}}, Lv.dev.n, [&](uint32_t a, uint32_t b, uint32_t a2, uint32_t b2) {
-      AmgLevelDev d = Lv.dev;
-      d.r0 = a;
-      d.r1 = b;
-      d.r2 = a2;
-      d.r3 = b2;
-      if (timed) {
-        const auto ev = prof_pair();
-        launch_amg_smooth(d, Lv.x, Lv.b, Lv.xt, stream, ev.first, ev.second, ntl);
-      } else {
-        launch_amg_smooth(d, Lv.x, Lv.b, Lv.xt, stream, nullptr, nullptr, ntl);
-      }
-    });
-    if (timed) prof_launches++;
-    std::swap(Lv.x, Lv.xt);
-  };
-  auto res = [&](int i) {
-    AmgGpuLevel& Lv = levels[i];
-    auto f = [&](uint32_t a, uint32_t b, uint32_t a2, uint32_t b2) {
-      AmgLevelDev d = Lv.dev;
-      d.r0 = a;
-      d.r1 = b;
-      d.r2 = a2;
-      d.r3 = b2;
-      launch_amg_residual(d, Lv.x, Lv.b, Lv.r, stream, (i == 0 && nt(2)) || (i == 1 && nt(64)));
-    };
-    if (Lv.dist) {
-      const CommScope cs(this, amg_cat(i));
-      overlapped(Lv.plan, {{Lv.x, 1}}, Lv.dev.n, f);
-    } else {
-      f(0, Lv.dev.n, 0, 0);
-    }
-  };
-  bool presmoothed = false;  // level i's zero-x pre-smoother already ran inside the restriction
-  for (int i = 0; i < down; ++i) {
-    AmgGpuLevel& Lv = levels[i];
-    if (presmoothed)
-      std::swap(Lv.x, Lv.xt);
-    else
-      sm(i, i > 0);  // coarse x was cleared by the restriction (ghosts too)
-    AmgGpuLevel& C = levels[i + 1];
-    // the next level is pre-smoothed by this loop: fuse its zero-x sweep into the restriction
-    presmoothed = (i + 1 < down) && (!Lv.dist || C.dist);
-    float* smo = presmoothed ? C.xt : nullptr;
-    if (presmoothed && (size_t)i < rr_pair.size() && rr_pair[i].nblocks && i + 2 <= down) {
-      // levels i and i + 1 in one launch; level i + 1 ends pre-smoothed (as
-      // the next iteration's swap leaves it) and level i + 2 gets its rhs
-      AmgGpuLevel& C2 = levels[i + 2];
-      const bool pre2 = i + 2 < down;  // both replicated / single-GPU: as `presmoothed` below
-      launch_amg_resrestrict_pair(Lv.dev, C.dev, rr_pair[i], Lv.x, Lv.b, C.b, C.xt, C2.b, C2.x,
-                                  pre2 ? C2.xt : nullptr, C2.dev.de, stream);
-      std::swap(C.x, C.xt);
-      presmoothed = pre2;
-      ++i;  // level i + 1 is done
-      continue;
-    }
-    if (!Lv.dist && Lv.dev.rr_agg) {
-      launch_amg_resrestrict(Lv.dev, Lv.x, Lv.b, C.b, C.x, smo, C.dev.de, stream);
-    } else if (!Lv.dist) {
-      res(i);
-      launch_amg_restrict(Lv.dev, Lv.r, C.b, C.x, 0, 0, 0, stream, smo, C.dev.de);
-    } else {
-      res(i);
-      // the restriction sums members owned by the next ranks too (their residuals
-      // are ghosts): the aggregates without such members overlap the exchange
-      const bool into_dist = C.dist;
-      float* cb = into_dist ? C.b : C.b + C.C0;
-      float* cx = into_dist ? C.x : C.x + C.C0;
-      const uint32_t sc = into_dist ? C.npad : Lv.dev.nc;
-      const uint32_t cg_lo = into_dist ? C.glo : (uint32_t)C.C0;
-      const uint32_t cg_hi = into_dist ? C.ghi : (uint32_t)(C.nglob - C.C1);
-      float* so = into_dist ? smo : nullptr;
-      if (amg_local) {  // partition-aware: every member is owned, no residual halo
-        launch_amg_restrict(Lv.dev, Lv.r, cb, cx, sc, cg_lo, cg_hi, stream, so, C.dev.de, 0, Lv.dev.nc, true);
-      } else {
-        const uint32_t split = Lv.dev.n >= overlap_min_rows ? Lv.rc_hi : 0u;  // as overlapped()
-        const CommScope cs(this, amg_cat(i));
-        halo_begin(Lv.plan, {{Lv.r, 1}});
-        if (split > 0)
-          launch_amg_restrict(Lv.dev, Lv.r, cb, cx, sc, cg_lo, cg_hi, stream, so, C.dev.de, 0, split, false);
-        halo_end();
-        launch_amg_restrict(Lv.dev, Lv.r, cb, cx, sc, cg_lo, cg_hi, stream, so, C.dev.de, split, Lv.dev.nc, true);
-      }
-    }
-    if (Lv.dist && !C.dist) {  // into the first replicated level: own slice, all-gather
-      std::vector<size_t> off(R + 1);
-      for (int q = 0; q <= R; ++q) off[q] = C.part[q] * sizeof(float);
-      timed_gather(kCommRepGather, off[rk + 1] - off[rk], [&] { comm->allgatherv_inplace(C.b, off, stream); });
-    }
-  }
-  if (tf < L && tf == tail_blob_first) {
-    launch_amg_tail_blob(d_tail, d_tail_desc, d_tail_blob, tail_blob_words, tail_vec_floats, tf, L, levels[tf].b,
-                         levels[tf].dev.n, stream);
-  } else if (tf < L) {
-    size_t lds = 0;  // LDS-resident tail when its vectors fit (CFD_AMG_TAIL=global: never)
-    for (int l = tf; l < L; ++l) lds += 4 * (((size_t)levels[l].dev.n + 3) & ~(size_t)3) * sizeof(float);
-    if (lds > lds_budget || tail_form == 0) lds = 0;
-    launch_amg_tail(d_tail, tf, L, lds, stream);
-  } else {
-    for (int s = 0; s < 10; ++s) sm(L - 1, s == 0 && L > 1);
-  }
-  for (int ii = down - 1; ii >= 0; --ii) {
-    // the prolongation reads aggregates seeded on lower ranks (ghosts of the coarse x)
-    if (levels[ii + 1].dist && amg_local) {  // partition-aware: every fine row's aggregate is owned
-      AmgGpuLevel& F = levels[ii];
-      launch_amg_prolong(F.dev, F.x, levels[ii + 1].x, stream, 0, F.dev.n, nt(32));
-    } else if (levels[ii + 1].dist) {  // the rows of owned aggregates overlap the coarse-x exchange
-      AmgGpuLevel& F = levels[ii];
-      const uint32_t split = F.dev.n >= overlap_min_rows ? F.pf_lo : F.dev.n;  // as overlapped()
-      const CommScope cs(this, amg_cat(ii + 1));
-      halo_begin(levels[ii + 1].plan, {{levels[ii + 1].x, 1}});
-      if (split < F.dev.n) launch_amg_prolong(F.dev, F.x, levels[ii + 1].x, stream, split, F.dev.n, nt(32));
-      halo_end();
-      if (split > 0) launch_amg_prolong(F.dev, F.x, levels[ii + 1].x, stream, 0, split, nt(32));
-    } else if (ii >= 1 && (size_t)ii < up_pair.size() && up_pair[ii].nblocks) {
-      // levels ii and ii - 1 post-smoothed in one launch; level ii's smoothed x
-      // lives only in the kernel's LDS (nothing reads it after the up-leg), its
-      // buffers swap as the separate launch would leave them
-      AmgGpuLevel &Cl = levels[ii], &F = levels[ii - 1];
-      launch_amg_prolong_smooth_pair(F.dev, Cl.dev, up_pair[ii], F.x, F.b, F.xt, Cl.x, Cl.b, levels[ii + 1].x, stream);
-      std::swap(Cl.x, Cl.xt);
-      std::swap(F.x, F.xt);
-      --ii;  // level ii - 1 is done
-      continue;
-    } else if (fused_prolong(ii)) {
-      // the prolongation applied inside the post-smoother's reads (x stays un-prolonged)
-      AmgGpuLevel& F = levels[ii];
-      launch_amg_smooth_prolong(F.dev, F.x, levels[ii + 1].x, F.b, F.xt, stream);
-      std::swap(F.x, F.xt);
-      continue;
-    } else {
-      launch_amg_prolong(levels[ii].dev, levels[ii].x, levels[ii + 1].x, stream, 0, 0, nt(32));
-    }
-    sm(ii, false, true);
-  }
-  // every level performs an even number of sweeps, so level 0 ends in p_sol
-  if (levels[0].x != p_sol) throw std::logic_error("AMG level-0 ping-pong parity");
 }
 
 // FGMRES Preconditioner Step (coupled_solver_fgmres.rs:1911-1994)
@@ -1605,11 +1033,7 @@ void Solver::precondition(int j, float* z) {
   // the prediction reads neighbours' r_u, r_v
   const CommScope cs(this, kCommKrylovHalo);
   overlapped(cell_plan, {{v, 3}}, N, [&](uint32_t a, uint32_t b, uint32_t a2, uint32_t b2) {
-    CoupledMatrix Ar = A;
-    Ar.r0 = a;
-    Ar.r1 = b;
-    Ar.r2 = a2;
-    Ar.r3 = b2;
+    const CoupledMatrix Ar = with_rows(A, a, b, a2, b2);
     launch_precond_predict(Ar, v, binv, j, dinv_uv, dinv_p, temp_p, p_sol, jacobi ? temp : nullptr, stream, nt(4));
   });
   bool in_sol = true;
@@ -1648,11 +1072,7 @@ void Solver::precondition(int j, float* z) {
   float* ps = in_sol ? p_sol : temp;
   // the velocity correction reads neighbours' p_sol
   overlapped(cell_plan, {{ps, 1}}, N, [&](uint32_t a, uint32_t b, uint32_t a2, uint32_t b2) {
-    CoupledMatrix Ar = A;
-    Ar.r0 = a;
-    Ar.r1 = b;
-    Ar.r2 = a2;
-    Ar.r3 = b2;
+    const CoupledMatrix Ar = with_rows(A, a, b, a2, b2);
     launch_precond_correct(Ar, v, binv, j, ps, dinv_uv, z, stream);
   });
 }
@@ -1689,38 +1109,6 @@ void Solver::set_reference_semantics(int flags) {
   ref_inplace = (flags & 1) != 0;
   ref_clamp = (flags & 8) != 0;
   ref_racy = (flags & 2) != 0;
-}
-
-// amg.rs:666-770 dispatch by dispatch (test mode, flags 1 / 8): pre-smooth,
-// residual + restriction (+ the clamped rows' store onto the last coarse
-// entry), the coarse x cleared, 10 coarsest sweeps, prolongation +
-// post-smooth -- no fused forms, no tail kernel.  In place (flag 1) the
-// smoother runs its workgroups in order; else out-of-place Jacobi.
-void Solver::v_cycle_reference() {
-  const int L = (int)levels.size();
-  auto smooth = [&](int i) {
-    AmgGpuLevel& Lv = levels[i];
-    if (ref_inplace) {
-      launch_amg_smooth_ordered(Lv.dev, Lv.x, Lv.b, stream);
-    } else {
-      launch_amg_smooth(Lv.dev, Lv.x, Lv.b, Lv.xt, stream);
-      std::swap(Lv.x, Lv.xt);
-    }
-  };
-  for (int i = 0; i + 1 < L; ++i) {
-    AmgGpuLevel &F = levels[i], &C = levels[i + 1];
-    smooth(i);
-    launch_amg_residual(F.dev, F.x, F.b, F.r, stream);
-    launch_amg_restrict(F.dev, F.r, C.b, C.x, 0, 0, 0, stream);  // coarse b = R r, coarse x = 0
-    const uint32_t nc = C.dev.n;
-    if (ref_clamp && nc % 64 != 0) CFD_HIP(hipMemsetAsync(C.b + nc - 1, 0, sizeof(float), stream));
-  }
-  for (int s = 0; s < 10; ++s) smooth(L - 1);
-  for (int i = L - 2; i >= 0; --i) {
-    launch_amg_prolong(levels[i].dev, levels[i].x, levels[i + 1].x, stream);
-    smooth(i);
-  }
-  if (levels[0].x != p_sol) throw std::logic_error("AMG level-0 ping-pong parity (reference semantics)");
 }
 
 void Solver::norm_launch(const float* v, int mode, int slot) {
@@ -2411,27 +1799,6 @@ void Solver::debug_buffer(int id, float* out) {
 }
 
 // ------------------------------------------------------------- accounting
-// algorithmic bytes of one level-ℓ smoother sweep in the
-// reference CSR/f32/u32 format: 4(n+1) + 8 nnz + 12 n.
-double Solver::smoother_bytes() const {
-  if (levels.empty()) return 0.0;
-  const double n = levels[0].dev.n, nnz = (double)levels[0].nnz;
-  return 4.0 * (n + 1.0) + 8.0 * nnz + 12.0 * n;
-}
-
-// Layout-true bytes of one level-0 sweep of k_amg_smooth: what the kernel
-// must move in the AmgLevelDev image -- the u8 row lengths, every ELL slot's
-// value and column (16-bit delta or i32) over the padded rows, b, x, the
-// smoother diagonal and x_out (4 B each per row; the x gathers at the
-// neighbours counted once, as SURVEY §8(d) counts them).  At C2 (w = 4,
-// 16-bit deltas) 41 B per row against the reference format's 56.
-double Solver::smoother_layout_bytes() const {
-  if (levels.empty()) return 0.0;
-  const AmgLevelDev& d = levels[0].dev;
-  const double st = d.stride, n = d.n;
-  return st + std::max(d.w, 1) * st * (4.0 + (d.use16 ? 2.0 : 4.0)) + 16.0 * n;
-}
-
 // Layout-true bytes of one step under the fixed schedule: per kernel, the
 // bytes its arrays in THIS library's layouts must move (each element once:
 // neighbour gathers counted once, as SURVEY §8(d) counts them), times its
@@ -2452,39 +1819,7 @@ double Solver::layout_step_bytes() const {
   const double spmv = (35 + 16 * ws) * Nn;                 // headers, cval_a + cval_g slots, x, y
   const double predict = (39 + 8 * ws) * Nn;               // headers, cval_g slots, V_j, dinv, temp_p / p_sol out
   const double correct = (34 + 8 * ws) * Nn;               // lg, cval_g slots, p_sol, V_j, dinv, Z_j out
-  // one V-cycle over the level images (as v_cycle launches them)
-  double vc = 0.0;
-  const int L = (int)levels.size();
-  const int down = std::min(std::max(tail_first, 1), L - 1);
-  auto row_image = [&](const AmgLevelDev& d) {  // ELL values + columns over the padded rows
-    return std::max(d.w, 1) * (double)d.stride * (4.0 + (d.use16 ? 2.0 : 4.0));
-  };
-  for (int i = 0; i < L; ++i) {
-    const AmgLevelDev& d = levels[i].dev;
-    const double n = d.n, st = d.stride, img = row_image(d);
-    const double smooth = st + img + 16 * n;
-    if (i < down) {
-      const double nc = levels[i + 1].dev.n;
-      // pre-smoother (coarse: zero-x, elementwise; not launched when fused into
-      // the previous level's restriction, whose 12 nc term counts it)
-      const bool presmoothed = i > 0 && (!levels[i - 1].dist || levels[i].dist);
-      vc += (i == 0 ? smooth : (presmoothed ? 0.0 : 12 * n));
-      if (d.rr_agg && !levels[i].dist)
-        vc += 4 * nc + 4 * n + 2 * st + img + 14 * n + 12 * nc;       // fused residual + restriction
-      else
-        vc += (2 * st + img + 16 * n) + (16 * nc + 4 * n + 12 * nc);  // residual, restriction
-      if (i > 0 && (size_t)i <= rr_pair.size() && rr_pair[i - 1].nblocks)
-        vc -= 8 * n;  // second level of a k_amg_resrestrict_pair: its b and x stay in LDS
-      if ((size_t)i < up_pair.size() && up_pair[i].nblocks)
-        vc -= 8 * n;  // coarse level of a k_amg_prolong_smooth_pair: its smoothed x stays in LDS
-      if (fused_prolong(i))
-        vc += smooth + 4 * n + 4 * nc;                                 // post-smoother reading x + P xc
-      else
-        vc += (12 * n + 4 * nc) + smooth;                              // prolongation, post-smoother
-    } else if (i == down) {
-      vc += 4.0 * tail_blob_words + 16.0 * tail_vec_floats;            // single-workgroup tail (LDS image in)
-    }
-  }
+  const double vc = v_cycle_layout_bytes();
   double inner = 0.0;
   for (int j = 0; j < M; ++j) {
     inner += predict + vc + correct + spmv;

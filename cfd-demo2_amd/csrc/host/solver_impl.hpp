@@ -189,6 +189,53 @@ struct UpPairPartition {
 bool build_up_pair_partition(const std::vector<uint32_t>& frow, const std::vector<uint32_t>& fcol,
                              const std::vector<uint32_t>& agg, uint32_t nc, uint32_t rows, uint32_t cap,
                              UpPairPartition& out);
+// The V-cycle's launch schedule: which launches one cycle makes, in order,
+// decided once per hierarchy (plan_v_cycle at the end of the AMG setup).
+// Solver::v_cycle runs it and Solver::v_cycle_layout_bytes prices it, op by
+// op.  How a row-partitioned level runs an op (halo overlap, split
+// restriction / prolongation) is the executor's business, not the plan's.
+struct VcLevel {               // what the decisions read of level i
+  bool dist = false;           // row-partitioned (a distributed rank's levels below amg_g)
+  bool fused_rr = false;       // takes k_amg_resrestrict (dev.rr_agg != 0)
+  bool down_pair = false;      // a k_amg_resrestrict_pair image of levels (i, i + 1) exists
+  bool up_pair = false;        // a k_amg_prolong_smooth_pair image of levels (i, i - 1) exists
+  bool fused_prolong = false;  // its post-smoother reads x + P x_c
+};
+enum class VcKind : uint8_t {
+  PreSmooth,          // flag: zero-x form (x was cleared by the restriction into the level)
+  TakePreSmoothed,    // the sweep ran inside the restriction into the level: its partner buffer becomes current
+  ResRestrictFused,   // k_amg_resrestrict; flag: also pre-smooths level + 1
+  ResidualRestrict,   // residual, then restriction; flag: also pre-smooths level + 1
+  ResRestrictPair,    // levels (level, level + 1) in one launch, level + 1 pre-smoothed; flag: also level + 2
+  GatherRhs,          // all-gather of the first replicated level's rhs
+  TailBlob,           // levels [level, L) in one workgroup from the LDS image
+  Tail,               // levels [level, L) in one workgroup
+  CoarsestSweeps,     // the ten sweeps of the last level (no tail)
+  Prolong,
+  PostSmooth,
+  PostSmoothProlong,  // post-smoother reading x + P x_c
+  ProlongSmoothPair,  // post-smoothers of levels (level, level - 1) in one launch
+};
+struct VcOp {
+  VcKind kind;
+  int level;
+  bool flag;
+};
+// levels [0, down) run the down and up legs; level `down` is the tail's first or the last level
+inline int v_cycle_down(int tail_first, int L) { return std::min(tail_first, L - 1); }
+// tail_first in [1, L] (L: no tail); tail_lds_image: the tail runs k_amg_tail_blob.
+// Pair flags are taken greedily (down leg from the top, up leg from the
+// bottom) and only where both levels run on their leg.
+std::vector<VcOp> plan_v_cycle(const std::vector<VcLevel>& lv, int tail_first, bool tail_lds_image);
+// the copy of an AmgLevelDev / CoupledMatrix restricted to rows [a, b) and [a2, b2)
+template <class T>
+T with_rows(T d, uint32_t a, uint32_t b, uint32_t a2, uint32_t b2) {
+  d.r0 = a;
+  d.r1 = b;
+  d.r2 = a2;
+  d.r3 = b2;
+  return d;
+}
 // Greedy index-order aggregation (amg.rs:84-116) of the pattern (row, col) of
 // n rows; returns the aggregate count, agg[i] = aggregate of row i, and
 // cpart = the aggregate partition induced by the row partition `part` (an
@@ -369,7 +416,7 @@ struct Solver {
   // AMG
   bool amg_built = false;
   int amg_setup_path = 0;          // 0 not built, 1 host, 2 device (build_amg_device)
-  int tail_first = 1;              // first AMG level handled by k_amg_tail
+  int tail_first = 1;              // first AMG level handled by k_amg_tail; after setup in [max(amg_g, 1), L]
   // tail kernel form (CFD_AMG_TAIL): 2 the LDS image of matrices + vectors
   // (k_amg_tail_blob, starting up to tail_blob_shift levels lower to fit),
   // 1 vectors in LDS (k_amg_tail_lds), 0 global memory (k_amg_tail); the
@@ -421,6 +468,17 @@ struct Solver {
   uint32_t tail_blob_words = 0, tail_vec_floats = 0;
   void build_tail_blob(int tf, bool reuse = false);  // reuse: rewrite the existing blob in place
   void set_resrestrict_blocks();
+  // A level's off-diagonal pattern as CSR in slot order, decoded from its ELL
+  // image (16-bit deltas included); val: the entries' values too.  One sync(),
+  // which also completes the downloads the caller queued before the call.
+  // False when a column lies outside the level's rows (a row-partitioned level).
+  bool level_csr(const AmgLevelDev& d, std::vector<uint32_t>& row, std::vector<uint32_t>& col,
+                 std::vector<float>* val = nullptr);
+  // the setup's last part (amg_cycle.cpp): fused-form choices, tail, pair
+  // images, and the V-cycle schedule they add up to
+  void finish_amg_schedule();
+  std::vector<VcOp> vc_plan;  // built by finish_amg_schedule, kept by refresh_amg, cleared by drop_amg
+  double v_cycle_layout_bytes() const;
   // down-leg pairs (k_amg_resrestrict_pair): rr_pair[i].nblocks > 0 when levels
   // i and i+1 run as one launch (single-GPU / replicated levels that both take
   // k_amg_resrestrict, level i+1 pre-smoothed)

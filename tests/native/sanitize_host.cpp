@@ -1,8 +1,10 @@
 // Host sanitizer driver for the product's host-side setup code (no GPU):
 // slab topology + halo plans for 1-4 ranks, and the host AMG hierarchy
 // (greedy aggregation, R = P^T, Galerkin products) with partition-aware
-// aggregation, on a cut-cell, a Voronoi and a Delaunay mesh.  Built with
-// ASan + UBSan by tests/test_sanitize.py; consistency checks on the way.
+// aggregation, and the V-cycle schedules planned over it, on a cut-cell, a
+// Voronoi and a Delaunay mesh.  Built with ASan + UBSan by
+// tests/test_sanitize.py; consistency checks on the way.
+#include <algorithm>
 #include <cstdio>
 #include <stdexcept>
 #include <vector>
@@ -34,6 +36,97 @@ cfd_mesh_view view_of(const cfd2::Mesh& x) {
 
 void check(bool ok, const char* what) {
   if (!ok) throw std::runtime_error(what);
+}
+
+// Invariants of a V-cycle schedule (plan_v_cycle) whatever the flags: sweeps
+// per level, every rhs produced once before its first reader, pairs only where
+// flagged and disjoint, levels from the tail on in one op.
+void check_schedule(const std::vector<cfd2::VcLevel>& lv, int tail_first, bool lds) {
+  using K = cfd2::VcKind;
+  const int L = (int)lv.size(), down = cfd2::v_cycle_down(tail_first, L);
+  const std::vector<cfd2::VcOp> ops = cfd2::plan_v_cycle(lv, tail_first, lds);
+  std::vector<int> sweeps(L, 0), rhs(L, 0), in_pair_down(L, 0), in_pair_up(L, 0);
+  rhs[0] = 1;  // level 0's rhs is bound by the caller
+  int bottom = 0;
+  auto reads = [&](int l) { check(l >= 0 && l < L && rhs[l] == 1, "op reads an rhs not produced exactly once"); };
+  for (const cfd2::VcOp& op : ops) {
+    const int i = op.level;
+    check(i >= 0 && i < L, "op level");
+    const bool tail_op = op.kind == K::TailBlob || op.kind == K::Tail || op.kind == K::CoarsestSweeps;
+    check(tail_op || i < down || (op.kind == K::GatherRhs && i == down),
+          "a level from the tail on outside the tail op");
+    switch (op.kind) {
+      case K::PreSmooth:
+        reads(i);
+        check(op.flag == (i > 0), "zero-x pre-smoother exactly on the coarse levels");
+        sweeps[i]++;
+        break;
+      case K::TakePreSmoothed:
+        reads(i);
+        check(sweeps[i] == 1, "takes a pre-smoothed buffer nothing produced");
+        break;
+      case K::ResRestrictFused:
+      case K::ResidualRestrict:
+        reads(i);
+        check((op.kind == K::ResRestrictFused) == (lv[i].fused_rr && !lv[i].dist), "fused restriction where flagged");
+        rhs[i + 1]++;
+        if (op.flag) sweeps[i + 1]++;
+        check(!op.flag || i + 1 < down, "fused pre-smoother of a level the down leg does not run");
+        break;
+      case K::ResRestrictPair:
+        reads(i);
+        check(lv[i].down_pair && i + 2 <= down, "down-leg pair without its flag or past the leg");
+        check(!in_pair_down[i] && !in_pair_down[i + 1], "down-leg pairs overlap");
+        in_pair_down[i] = in_pair_down[i + 1] = 1;
+        rhs[i + 1]++;
+        rhs[i + 2]++;
+        sweeps[i + 1]++;
+        if (op.flag) sweeps[i + 2]++;
+        check(!op.flag || i + 2 < down, "fused pre-smoother of a level the down leg does not run");
+        break;
+      case K::GatherRhs:
+        check(i >= 1 && lv[i - 1].dist && !lv[i].dist && rhs[i] == 1, "gather into the first replicated level");
+        break;
+      case K::TailBlob:
+      case K::Tail:
+        reads(i);
+        check(i == tail_first && tail_first < L && (op.kind == K::TailBlob) == lds, "tail op");
+        bottom++;
+        break;
+      case K::CoarsestSweeps:
+        reads(i);
+        check(i == L - 1 && tail_first == L, "coarsest sweeps only without a tail, on the last level");
+        sweeps[i] += 10;
+        bottom++;
+        break;
+      case K::Prolong:
+        check(bottom == 1 && sweeps[i] == 1, "prolongation after the bottom, before the post-smoother");
+        break;
+      case K::PostSmooth:
+      case K::PostSmoothProlong:
+        reads(i);
+        check(bottom == 1, "post-smoother before the bottom");
+        check(op.kind == K::PostSmooth || (lv[i].fused_prolong && !lv[i + 1].dist), "fused prolongation where flagged");
+        sweeps[i]++;
+        break;
+      case K::ProlongSmoothPair:
+        reads(i);
+        reads(i - 1);
+        check(bottom == 1 && i >= 1 && lv[i].up_pair, "up-leg pair without its flag");
+        check(!in_pair_up[i] && !in_pair_up[i - 1], "up-leg pairs overlap");
+        in_pair_up[i] = in_pair_up[i - 1] = 1;
+        sweeps[i]++;
+        sweeps[i - 1]++;
+        break;
+    }
+  }
+  check(bottom == 1, "exactly one bottom op");
+  for (int l = 0; l < L; ++l) {
+    if (l < down) check(sweeps[l] == 2, "a level above the tail is swept twice (even: ping-pong parity)");
+    if (l <= down) check(rhs[l] == 1, "every level's rhs produced exactly once");
+    if (l >= tail_first) check(sweeps[l] == 0, "a tail level swept outside the tail op");
+  }
+  if (tail_first == L) check(sweeps[L - 1] == 10, "ten coarsest sweeps");
 }
 
 void run(const char* name, const cfd2::Mesh& m) {
@@ -186,6 +279,28 @@ void run(const char* name, const cfd2::Mesh& m) {
     for (size_t l = 0; l < H.size(); ++l) {  // coarse rows follow their seeds: a partition in rank order
       check(H[l].part.size() == (size_t)R + 1 && H[l].part[0] == 0 && H[l].part[R] == H[l].A.rows, "level partition");
       for (int q = 0; q < R; ++q) check(H[l].part[q] <= H[l].part[q + 1], "level partition order");
+    }
+    {  // V-cycle schedules over this hierarchy: its big levels row-partitioned when R > 1
+      const int L = (int)H.size();
+      std::vector<cfd2::VcLevel> lv(L);
+      int g = 0;  // first replicated level
+      for (int l = 0; l < L; ++l) {
+        lv[l].dist = R > 1 && H[l].A.rows > 200;
+        if (lv[l].dist) g = l + 1;
+        lv[l].fused_rr = !lv[l].dist && l + 1 < L && l % 3 != 2;  // some levels keep the two kernels
+        lv[l].fused_prolong = !lv[l].dist;
+      }
+      check_schedule(lv, L, false);  // no tail, no pairs
+      for (int l = 0; l < L; ++l) {  // every adjacent pair of replicated levels flagged
+        lv[l].down_pair = !lv[l].dist;
+        lv[l].up_pair = l >= 1 && !lv[l - 1].dist;
+      }
+      check_schedule(lv, L, false);
+      const int mid = std::max({g, 1, L / 2});  // tail from a middle level, either kind
+      check_schedule(lv, mid, true);
+      check_schedule(lv, mid, false);
+      std::printf("%s: %d rank(s): V-cycle schedules over %d levels (%d row-partitioned), tail from %d: ok\n", name, R,
+                  L, g, mid);
     }
     std::printf("%s: %u cells, %d rank(s): nnz %llu, halo %llu, regular coupled rows %llu, %zu AMG levels: ok\n",
                 name, n, R, (unsigned long long)nnz, (unsigned long long)sends, (unsigned long long)reg_rows,
