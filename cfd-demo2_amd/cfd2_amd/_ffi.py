@@ -132,6 +132,26 @@ class CommStats(C.Structure):  # cfd_comm_stats
 TRANSPORTS = {0: "none", 1: "rccl", 2: "in-process", 3: "host-staged"}
 
 
+class FlowDiag(C.Structure):  # cfd_flow_diag
+    _fields_ = [
+        ("max_speed", C.c_double),
+        ("max_vorticity", C.c_double),
+        ("max_divergence", C.c_double),
+        ("kinetic_energy", C.c_double),
+        ("enstrophy", C.c_double),
+        ("force_pressure", C.c_double * 2),
+        ("force_viscous", C.c_double * 2),
+        ("region_faces", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return dict(max_speed=self.max_speed, max_vorticity=self.max_vorticity,
+                    max_divergence=self.max_divergence, kinetic_energy=self.kinetic_energy,
+                    enstrophy=self.enstrophy, force_pressure=tuple(self.force_pressure),
+                    force_viscous=tuple(self.force_viscous), region_faces=self.region_faces)
+
+
 class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     _fields_ = [
         ("magic", C.c_char * 8),
@@ -195,6 +215,8 @@ EXPORTED = [
     "cfd_dist_info", "cfd_dist_plan", "cfd_debug_rccl_selftest", "cfd_debug_comm_watchdog", "cfd_dist_comm_stats",
     "cfd_debug_group_fault", "cfd_debug_group_fault_midstep", "cfd_group_reset", "cfd_group_needs_restore",
     "cfd_comm_timing_enable", "cfd_comm_timing",
+    "cfd_flow_diagnostics", "cfd_get_derived", "cfd_set_force_region", "cfd_min_cell_size",
+    "cfd_adaptive_dt_rule", "cfd_adapt_dt", "cfd_group_flow_diagnostics", "cfd_group_adapt_dt",
 ]
 
 _lib = None

@@ -97,6 +97,15 @@ def _bind():
     L.cfd_group_needs_restore.restype = C.c_int32
     L.cfd_comm_timing_enable.argtypes = [_vp, C.c_int32]
     L.cfd_comm_timing.argtypes = [_vp, C.POINTER(_ffi.CommTimingEntry), C.c_int32, C.POINTER(C.c_int32)]
+    L.cfd_flow_diagnostics.argtypes = [_vp, C.POINTER(_ffi.FlowDiag)]
+    L.cfd_get_derived.argtypes = [_vp, C.c_int32, dp]
+    L.cfd_set_force_region.argtypes = [_vp, C.c_double, C.c_double, C.c_double, C.c_double, u32p]
+    L.cfd_min_cell_size.argtypes = [_vp]
+    L.cfd_min_cell_size.restype = C.c_double
+    L.cfd_adaptive_dt_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, dp, C.POINTER(C.c_int32)]
+    L.cfd_adapt_dt.argtypes = [_vp, C.c_double, C.POINTER(C.c_float)]
+    L.cfd_group_flow_diagnostics.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(_ffi.FlowDiag)]
+    L.cfd_group_adapt_dt.argtypes = [C.POINTER(_vp), C.c_int32, C.c_double, C.POINTER(C.c_float)]
     _bound = True
     return L
 
@@ -270,6 +279,47 @@ class GpuSolver:
         self._call("cfd_get_d_p", a.ctypes.data_as(C.POINTER(C.c_double)))
         return a
 
+    # -- flow diagnostics, derived fields, adaptive dt (one read-only GPU pass) --
+    def flow_diagnostics(self) -> _ffi.FlowDiag:
+        """cfd_flow_diagnostics: max speed / vorticity / divergence, kinetic
+        energy, enstrophy and the force on the selected wall faces of the
+        current state (collective on a distributed rank)."""
+        d = _ffi.FlowDiag()
+        self._call("cfd_flow_diagnostics", C.byref(d))
+        return d
+
+    def _derived(self, kind) -> np.ndarray:
+        a = np.zeros(self.num_cells)
+        self._call("cfd_get_derived", int(kind), a.ctypes.data_as(C.POINTER(C.c_double)))
+        return a
+
+    def speed(self) -> np.ndarray: return self._derived(0)
+    def vorticity(self) -> np.ndarray: return self._derived(1)
+    def divergence(self) -> np.ndarray: return self._derived(2)
+
+    def set_force_region(self, x0, y0, x1, y1) -> int:
+        """Select the wall faces whose centre lies in the closed box (x1 < x0:
+        none) for the force sums; returns the faces selected over the whole mesh."""
+        n = C.c_uint32()
+        self._call("cfd_set_force_region", float(x0), float(y0), float(x1), float(y1), C.byref(n))
+        return int(n.value)
+
+    @property
+    def min_cell_size(self) -> float:
+        """min sqrt(cell_vol) over the whole mesh (the reference's actual_min_cell_size)."""
+        return float(_ffi.lib().cfd_min_cell_size(self._h))
+
+    def adapt_dt(self, target_cfl) -> float:
+        """The reference's adaptive time step from the current state; returns the dt now set."""
+        dt = C.c_float()
+        self._call("cfd_adapt_dt", float(target_cfl), C.byref(dt))
+        return float(dt.value)
+
+    def step_adaptive(self, target_cfl) -> float:
+        """step(), then adapt_dt(target_cfl): one turn of the reference's driver loop."""
+        self.step()
+        return self.adapt_dt(target_cfl)
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -409,6 +459,16 @@ class GpuSolver:
         return out
 
 
+def adaptive_dt_rule(current_dt, target_cfl, min_cell_size, max_vel):
+    """cfd_adaptive_dt_rule, the reference's driver-loop rule (src/ui/app.rs:897-909)
+    in f64; no handle and no GPU needed.  Returns (next_dt, changed)."""
+    L = _bind()
+    nxt, ch = C.c_double(), C.c_int32()
+    _ffi.check(L.cfd_adaptive_dt_rule(float(current_dt), float(target_cfl), float(min_cell_size), float(max_vel),
+                                      C.byref(nxt), C.byref(ch)), "cfd_adaptive_dt_rule")
+    return float(nxt.value), bool(ch.value)
+
+
 def dist_unique_id() -> bytes:
     """RCCL unique id (rank 0 creates it, every rank passes it to create_dist)."""
     L = _bind()
@@ -504,6 +564,37 @@ class GpuGroup:
     def get_u(self): return self._gather("get_u", 2)
     def get_p(self): return self._gather("get_p", 1)
     def get_d_p(self): return self._gather("get_d_p", 1)
+
+    # diagnostics: the group calls are collective; every rank returns the same bytes
+    def flow_diagnostics(self) -> _ffi.FlowDiag:
+        out = (_ffi.FlowDiag * self.nranks)()
+        _ffi.check(_bind().cfd_group_flow_diagnostics(self._harr, self.nranks, out), "cfd_group_flow_diagnostics")
+        first = bytes(out[0])
+        assert all(bytes(out[r]) == first for r in range(self.nranks)), "ranks disagree on the flow diagnostics"
+        return _ffi.FlowDiag.from_buffer_copy(first)
+
+    # derived fields: per rank, not collective (the pass reads current ghosts)
+    def speed(self): return self._gather("speed", 1)
+    def vorticity(self): return self._gather("vorticity", 1)
+    def divergence(self): return self._gather("divergence", 1)
+
+    def set_force_region(self, x0, y0, x1, y1) -> int:
+        return [r.set_force_region(x0, y0, x1, y1) for r in self.ranks][0]
+
+    @property
+    def min_cell_size(self) -> float:
+        return self.ranks[0].min_cell_size
+
+    def adapt_dt(self, target_cfl) -> float:
+        dt = C.c_float()
+        _ffi.check(_bind().cfd_group_adapt_dt(self._harr, self.nranks, float(target_cfl), C.byref(dt)),
+                   "cfd_group_adapt_dt")
+        return float(dt.value)
+
+    def step_adaptive(self, target_cfl) -> float:
+        self.step()
+        return self.adapt_dt(target_cfl)
+
     def step_info(self): return self.ranks[0].step_info()
     def amg_levels(self): return self.ranks[0].amg_levels()
 

@@ -3040,11 +3040,11 @@ __global__ void __launch_bounds__(kBlock) k_evolution_partial(StateView cur, Sta
   }
 }
 
-__global__ void __launch_bounds__(kRedFinalThreads) k_evolution_final(RedSrcD r, double* out5) {
+__global__ void __launch_bounds__(kRedFinalThreads) k_evolution_final(RedSrcD r, double* out) {
   __shared__ double la[kRedMaxSegments], lb[65];
-  for (int f = 0; f < 5; ++f) {
-    const double t = red_total<double, kRedFinalThreads>(r, (uint32_t)f, la, lb);
-    if (threadIdx.x == 0) out5[f] = t;
+  for (uint32_t f = 0; f < r.nvec; ++f) {
+    const double t = red_total<double, kRedFinalThreads>(r, f, la, lb);
+    if (threadIdx.x == 0) out[f] = t;
   }
 }
 
@@ -3412,8 +3412,8 @@ void launch_seg_reduce_d(const double* part, uint32_t np, uint32_t nchunks, uint
 void launch_max_combine(const uint32_t* gathered, int R, uint32_t* out, uint32_t* host_out, hipStream_t s) {
   hipLaunchKernelGGL(k_max_combine, dim3(1), dim3(64), 0, s, gathered, R, out, host_out);
 }
-void launch_evolution_final(const RedSrcD& r, double* out5, hipStream_t s) {
-  hipLaunchKernelGGL(k_evolution_final, dim3(1), dim3(kRedFinalThreads), 0, s, r, out5);
+void launch_evolution_final(const RedSrcD& r, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_evolution_final, dim3(1), dim3(kRedFinalThreads), 0, s, r, out);
 }
 
 void build_r_m4(const std::vector<uint32_t>& r_row, const std::vector<uint32_t>& r_col, std::vector<int32_t>& out) {

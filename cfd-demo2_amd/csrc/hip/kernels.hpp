@@ -471,7 +471,38 @@ void launch_seg_reduce(const float* part, uint32_t np, uint32_t nchunks, uint32_
 void launch_seg_reduce_d(const double* part, uint32_t np, uint32_t nchunks, uint32_t G, int nvec, double* out,
                          uint32_t maxseg, hipStream_t s);
 void launch_max_combine(const uint32_t* gathered, int R, uint32_t* out, uint32_t* host_out, hipStream_t s);
-// out5[f] = total of the 5 check_evolution sums (r.nvec = 5)
-void launch_evolution_final(const RedSrcD& r, double* out5, hipStream_t s);
+// out[f] = total of vector f of r, f < r.nvec (check_evolution: 5 sums; flow diagnostics: 6)
+void launch_evolution_final(const RedSrcD& r, double* out, hipStream_t s);
+
+// ---- flow diagnostics (diagnostics.hip) ----
+// One read-only sweep over the owned cells of a state: Green-Gauss gradients of
+// u as k_prepare forms them (the same bits), omega = dv/dx - du/dy and div =
+// du/dx + dv/dy per cell, and per cell the f64 terms (each evaluated left to
+// right from the f32 values)
+//   0 kinetic energy 0.5 vol s, s = (double)u u + (double)v v
+//   1 enstrophy      0.5 vol omega omega
+//   2, 3 pressure force  sum over the selected wall slots of p n_x area, p n_y area
+//   4, 5 viscous force   ... of viscosity u area / dist_e, viscosity v area / dist_e
+// as unit partials partial[f * np + k] of the canonical tree, plus the maxima
+// of s, |omega|, |div| as bit patterns (a NaN never becomes the maximum).
+constexpr int kFlowDiagSums = 6;
+struct FlowDiagArgs {
+  uint32_t N;
+  cfd_constants c;
+  FaceSlots fs;
+  const float* vol;
+  const float2* u;            // owned base; neighbours through fs.other (ghosts current)
+  const float* p;
+  const uint16_t* wall_mask;  // [N] bit k: wall slot k is in the force region; null: no region (forces +0)
+  float* omega_out;           // [N] or null (both null: the scalar-only pass)
+  float* div_out;
+  uint32_t U;                 // chunks per unit (RedGeom::U)
+  uint32_t np;                // unit partials per sum
+  double* partial;            // [kFlowDiagSums * np]
+  unsigned long long* blockmax;  // [3 * flow_diag_blocks(N)] scratch
+};
+uint32_t flow_diag_blocks(uint32_t N);
+// maxout[0..2] = bits of max s (f64), max |omega|, max |div| (f32 bits, zero-extended)
+void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s);
 
 }  // namespace cfd2

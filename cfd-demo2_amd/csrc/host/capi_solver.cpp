@@ -475,6 +475,55 @@ cfd_status cfd_group_state_save(cfd_solver* const* h, int32_t n, const char* pat
   return group_run(h, n, [path](cfd2::Solver& s) { s.save_state(path); });
 }
 
+// ------------------------------------------------------- flow diagnostics
+cfd_status cfd_flow_diagnostics(cfd_solver* s, cfd_flow_diag* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->flow_diagnostics(out); });
+}
+cfd_status cfd_get_derived(cfd_solver* s, int32_t kind, double* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  if (kind < 0 || kind > 2) return set_error(CFD_ERR_INVALID, "derived field kind must be 0, 1 or 2");
+  return guard([&] { s->s->get_derived(kind, out); });
+}
+cfd_status cfd_set_force_region(cfd_solver* s, double x0, double y0, double x1, double y1, uint32_t* faces) {
+  CHECK_S(s);
+  return guard([&] {
+    const uint32_t n = s->s->set_force_region(x0, y0, x1, y1);
+    if (faces) *faces = n;
+  });
+}
+double cfd_min_cell_size(const cfd_solver* s) { return (s && s->s) ? s->s->min_cell : 0.0; }
+cfd_status cfd_adaptive_dt_rule(double current_dt, double target_cfl, double min_cell_size, double max_vel,
+                                double* next_dt, int32_t* changed) {
+  if (!next_dt || !changed) return set_error(CFD_ERR_INVALID, "null out");
+  *changed = cfd2::adaptive_dt_rule(current_dt, target_cfl, min_cell_size, max_vel, next_dt) ? 1 : 0;
+  return CFD_OK;
+}
+cfd_status cfd_adapt_dt(cfd_solver* s, double target_cfl, float* new_dt) {
+  CHECK_S(s);
+  return guard([&] {
+    const float dt = s->s->adapt_dt(target_cfl);
+    if (new_dt) *new_dt = dt;
+  });
+}
+// read-only collectives: refused on a group that needs restore (its ranks
+// stopped at different points of a step), never the cause of that mark
+cfd_status cfd_group_flow_diagnostics(cfd_solver* const* h, int32_t n, cfd_flow_diag* out) {
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  if (cfd_group_needs_restore(h, n))
+    return set_error(CFD_ERR_INVALID, "group flow diagnostics refused: the group needs restore after a failed step");
+  return group_run(h, n, [out](cfd2::Solver& s) { s.flow_diagnostics(out + s.rk); });
+}
+cfd_status cfd_group_adapt_dt(cfd_solver* const* h, int32_t n, double target_cfl, float* new_dt) {
+  if (cfd_group_needs_restore(h, n))
+    return set_error(CFD_ERR_INVALID, "group adapt_dt refused: the group needs restore after a failed step");
+  const cfd_status st = group_run(h, n, [target_cfl](cfd2::Solver& s) { s.adapt_dt(target_cfl); });
+  if (st == CFD_OK && new_dt) *new_dt = h[0]->s->constants.dt;
+  return st;
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

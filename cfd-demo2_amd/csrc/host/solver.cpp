@@ -68,6 +68,16 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
   build_topology(mesh, topo, (uint32_t)starts[rk], (uint32_t)starts[rk + 1]);
   N = topo.N;
   F = topo.F;
+  // flow diagnostics (diagnostics.cpp): the host data the mesh view is needed for
+  min_cell = std::numeric_limits<double>::infinity();
+  for (uint32_t i = 0; i < NG; ++i) min_cell = std::fmin(min_cell, std::sqrt(mesh.cell_vol[i]));
+  for (uint32_t i = 0; i < NG; ++i)
+    for (uint32_t k = mesh.cell_face_offsets[i]; k < mesh.cell_face_offsets[i + 1]; ++k) {
+      const uint32_t f = mesh.cell_faces[k];
+      if (f >= mesh.num_faces) throw std::invalid_argument("cell_faces out of range");
+      if (mesh.face_neighbor[f] == UINT32_MAX && (mesh.face_boundary[f] & 3u) == 3u)
+        wall_faces.push_back({mesh.face_cx[f], mesh.face_cy[f], i, k - mesh.cell_face_offsets[i]});
+    }
   red = red_geom(NG);
   if (red.nseg > kRedMaxSegments)
     throw std::invalid_argument("mesh too large for the reduction tree (at most 268 M cells)");
@@ -473,7 +483,11 @@ RedSrc Solver::combine(const float* part, int nvec) {
   return r;
 }
 
-RedSrcD Solver::combine_d(const double* part, int nvec) {
+RedSrcD Solver::combine_d(const double* part, int nvec, double* local, double* gather) {
+  if (!local) {
+    local = red_local_d;
+    gather = red_gather_d;
+  }
   RedSrcD r;
   r.G = red.G / red.U;  // units per segment
   r.nseg = red.nseg;
@@ -484,10 +498,10 @@ RedSrcD Solver::combine_d(const double* part, int nvec) {
     r.nchunks = nunits;
     return r;
   }
-  launch_seg_reduce_d(part, pstride, nunits, r.G, nvec, red_local_d, maxseg, stream);
+  launch_seg_reduce_d(part, pstride, nunits, r.G, nvec, local, maxseg, stream);
   const size_t bytes = (size_t)nvec * maxseg * sizeof(double);
-  timed_gather(kCommReduceGather, bytes, [&] { comm->allgather(red_local_d, red_gather_d, bytes, stream); });
-  r.p = red_gather_d;
+  timed_gather(kCommReduceGather, bytes, [&] { comm->allgather(local, gather, bytes, stream); });
+  r.p = gather;
   r.stride = maxseg;
   r.seg_src = d_seg_src;
   return r;

@@ -600,6 +600,31 @@ struct Solver {
   void get_global_ids(uint32_t* c0, uint32_t* c1) const { *c0 = topo.c0; *c1 = topo.c1; }
   size_t debug_len(int id) const;
   void debug_buffer(int id, float* out);
+  // ---- flow diagnostics (diagnostics.cpp; kernels.hpp FlowDiagArgs) ----
+  // Read-only on the current state; every device buffer below is allocated on
+  // first use.  Collective on a distributed solver (the ghosts of u are current
+  // after set_u, step and load_state); R ranks give one GPU's bits.
+  struct WallFace {     // every wall face of the WHOLE mesh, f64 centre
+    double cx, cy;
+    uint32_t cell;      // global owner cell
+    uint32_t slot;      // its slot in the owner's face list
+  };
+  std::vector<WallFace> wall_faces;
+  double min_cell = 0.0;             // min sqrt(cell_vol) over the whole mesh (f64)
+  double* diag_partial = nullptr;    // [6 * pstride] unit partials
+  unsigned long long* diag_blockmax = nullptr;
+  uint64_t* diag_res = nullptr;      // [0, 6) sums (f64), [6, 9) this rank's maxima, [9, 9 + 3R) gathered
+  double* diag_red_local = nullptr;  // distributed: segment values of the 6 sums
+  double* diag_red_gather = nullptr;
+  float* diag_omega = nullptr;       // [N] field outputs (first cfd_get_derived)
+  float* diag_div = nullptr;
+  uint16_t* diag_mask = nullptr;     // [N] selected wall slots (first non-empty force region)
+  bool region_on = false;
+  uint32_t region_faces = 0;         // selected wall faces, whole mesh
+  void flow_diagnostics(cfd_flow_diag* out, bool fields = false);
+  void get_derived(int kind, double* out);
+  uint32_t set_force_region(double x0, double y0, double x1, double y1);
+  float adapt_dt(double target_cfl);
   double algorithmic_step_bytes() const;
   double layout_step_bytes() const;
   double smoother_bytes() const;
@@ -782,8 +807,13 @@ struct Solver {
   // partials part[v * nchunks + k]: the partials themselves on one GPU; on a
   // distributed rank its segment values are computed and all-gathered first
   RedSrc combine(const float* part, int nvec);
-  RedSrcD combine_d(const double* part, int nvec);
+  // local / gather: segment-value buffers of a distributed rank (default: check_evolution's, 5 vectors)
+  RedSrcD combine_d(const double* part, int nvec, double* local = nullptr, double* gather = nullptr);
   void make_plan_buffers(HaloPlan& p, int max_comps);
 };
+
+// The reference's adaptive time-step rule (src/ui/app.rs:897-909), f64; false
+// (and *next_dt = current_dt) when max_vel <= 1e-6 leaves dt alone.
+bool adaptive_dt_rule(double current_dt, double target_cfl, double min_cell_size, double max_vel, double* next_dt);
 
 }  // namespace cfd2

@@ -472,6 +472,63 @@ cfd_status cfd_dist_plan(const cfd_mesh_view* mesh, int32_t nranks, int32_t rank
                          uint32_t* num_send, uint32_t* ghost_global, int32_t* peer_rank,
                          uint32_t* peer_recv, uint32_t* peer_send, uint32_t* send_global);
 
+/* ------------------------------------------------------------------------ */
+/* Flow diagnostics, derived fields and the adaptive time step: what the
+ * reference's driver loop does on the host after every step (src/ui/app.rs:
+ * 871-910: read u back, max_vel = max sqrt(vx^2 + vy^2), dt = target_cfl *
+ * min_cell_size / max_vel limited to 1.2x growth and [1e-9, 100]) as one
+ * read-only pass over the current state on the GPU.  Nothing cfd_step reads is
+ * written; a handle that never calls these launches and allocates nothing.
+ * Per cell, in f32 with the step's own arithmetic: the Green-Gauss velocity
+ * gradients g_u, g_v exactly as prepare_coupled forms them (inlet face value
+ * inlet_velocity * smoothstep(0, ramp_time, time) of the current constants,
+ * wall 0, outlet the cell value), omega = g_v.x - g_u.y, div = g_u.x + g_v.y.
+ * Maxima ignore NaN cells (the reference's `if v > max_vel`).  Sums are f64
+ * in the canonical reduction order, so a distributed solver returns one
+ * GPU's bits on every rank.
+ * Wall force: of the fluid on the wall faces selected by cfd_set_force_region,
+ * consistent with the assembly (wall face pressure = cell pressure, wall
+ * diffusion = viscosity * area / |face centre - cell centre|), n out of the
+ * cell: pressure sum p n area, viscous sum viscosity * u * area / dist.       */
+typedef struct cfd_flow_diag {
+  double max_speed;        /* sqrt (host, f64) of the device max of (double)u u + (double)v v: the reference's max_vel */
+  double max_vorticity;    /* max |omega_i| */
+  double max_divergence;   /* max |div_i|   */
+  double kinetic_energy;   /* sum 0.5 vol (u^2 + v^2)   (per unit density) */
+  double enstrophy;        /* sum 0.5 vol omega^2 */
+  double force_pressure[2];
+  double force_viscous[2];
+  uint32_t region_faces;   /* wall faces selected, whole mesh */
+  uint32_t reserved;
+} cfd_flow_diag;
+/* Collective on a distributed handle (every rank gets the same bytes).      */
+cfd_status cfd_flow_diagnostics(cfd_solver* s, cfd_flow_diag* out);
+/* kind 0 speed, 1 vorticity, 2 divergence of the owned cells, widened to f64
+ * (runs the pass with its field outputs on; not collective)                 */
+cfd_status cfd_get_derived(cfd_solver* s, int32_t kind, double* out /* [N owned] */);
+/* Selects the wall faces (boundary 3) whose f64 centre lies in the closed box
+ * [x0, x1] x [y0, y1]; x1 < x0 selects none.  *faces (optional) = faces
+ * selected over the whole mesh.  Distributed solver: call it on every rank
+ * with the same box (not collective).                                       */
+cfd_status cfd_set_force_region(cfd_solver* s, double x0, double y0, double x1, double y1, uint32_t* faces);
+/* min sqrt(cell_vol), f64, over the WHOLE mesh (app.rs:377-381); 0 for null */
+double cfd_min_cell_size(const cfd_solver* s);
+/* app.rs:897-909 in f64, no handle: *changed = 0 and *next_dt = current_dt
+ * unless max_vel > 1e-6; else next = target_cfl * min_cell_size / max_vel,
+ * capped at current_dt * 1.2, clamped to [1e-9, 100].                       */
+cfd_status cfd_adaptive_dt_rule(double current_dt, double target_cfl, double min_cell_size, double max_vel,
+                                double* next_dt, int32_t* changed);
+/* cfd_flow_diagnostics -> the rule with current_dt = (double)constants.dt ->
+ * cfd_set_dt((float)next) (which keeps the dt_old rule); *new_dt (optional) =
+ * constants.dt afterwards.  Collective on a distributed handle: every rank
+ * sets the same value.                                                      */
+cfd_status cfd_adapt_dt(cfd_solver* s, double target_cfl, float* new_dt);
+/* In-process group: the two collectives on every rank (one host thread
+ * each).  They do not change the state, so a failure never marks the group
+ * needs-restore; a group already marked returns CFD_ERR_INVALID.            */
+cfd_status cfd_group_flow_diagnostics(cfd_solver* const* handles, int32_t nranks, cfd_flow_diag* out /* [nranks] */);
+cfd_status cfd_group_adapt_dt(cfd_solver* const* handles, int32_t nranks, double target_cfl, float* new_dt);
+
 #ifdef __cplusplus
 }
 #endif
