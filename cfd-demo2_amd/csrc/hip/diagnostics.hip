@@ -6,43 +6,18 @@
 // reduction order (kernels.hpp).  Nothing the step reads is written.
 #include <hip/hip_runtime.h>
 
+#include "device_util.hpp"
 #include "kernels.hpp"
+#include "reduce_dev.hpp"
 
 namespace cfd2 {
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr uint32_t kBlockCells = 4 * kRedChunkCells;  // one block: 4 chunks of 256 cells
 
-// prepare_coupled.wgsl's smoothstep as kernels.hip restates it (same operations)
-__device__ __forceinline__ float wsmoothstep(float lo, float hi, float x) {
-  const float t = fminf(fmaxf((x - lo) / (hi - lo), 0.0f), 1.0f);
-  return t * t * (3.0f - 2.0f * t);
-}
-
-// XCD-aware block -> tile remap (kernels.hip xcd_block): XCD k sweeps a
-// contiguous range of cells, so the u[other] gathers hit its L2.  Order only.
-__device__ __forceinline__ uint32_t xcd_block() {
-  const uint32_t b = blockIdx.x, nb = gridDim.x;
-  const uint32_t xcd = b & 7u, q = nb >> 3, r = nb & 7u;
-  const uint32_t base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (b >> 3);
-}
-
-// canonical pairwise tree over the wavefront's 64 consecutive cells (lane 0: root)
-__device__ __forceinline__ double wave_tree(double v) {
-  for (uint32_t st = 1; st < 64; st <<= 1) v = v + __shfl_down(v, st);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long w = (unsigned long long)__shfl_xor((long long)v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
+// The blocks are remapped per XCD (xcd_block): XCD k sweeps a contiguous range
+// of cells, so the u[other] gathers hit its L2.  Order only.
 // Thread t of block b handles cells b*1024 + q*256 + t, q = 0..3 (every load of
 // a face slot is one coalesced wavefront access): chunk q of the block is its
 // 256 cells of round q, wavefront w the chunk's quarter w.  Sums: the
@@ -84,7 +59,10 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
         const uint32_t bt = meta & kMetaBtypeMask;
         const float area = fs.area[e];
         const float nx = fs.nx[e], ny = fs.ny[e];  // oriented out of this cell
-        // face value of u per face type: k_prepare's (prepare_coupled.wgsl:281-324)
+        // face value of u per face type: a copy of prepare_cell's branch (flux.hip;
+        // prepare_coupled.wgsl:281-324).  One shared function changed k_prepare's
+        // register allocation, so the two copies stay, held together by
+        // tests/test_gpu_flow_diag.py's k_prepare-bits test.
         float vfu, vfv;
         if (other != kNoCell) {
           const float2 uo = a.u[other];

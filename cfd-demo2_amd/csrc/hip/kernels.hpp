@@ -210,7 +210,7 @@ struct AmgLevelDev {
   uint32_t stride;       // row stride of the ELL slots (n rounded up to 64)
   int w;                 // ELL width (max off-diagonals per row)
   int use16;             // 1: col16 holds deltas; 0: col32 holds absolute columns
-  int full;              // slot-load mode of the row kernels (kernels.hip gather_group): 0 or 1
+  int full;              // slot-load mode of the row kernels (amg_rows.hpp gather_group): 0 or 1
   const float* val;      // [r*stride + i]
   const int16_t* col16;  // [r*stride + i]  col - i
   const int32_t* col32;  // [r*stride + i] signed local column
@@ -293,7 +293,7 @@ struct PackArgs {
   float* stage;
 };
 
-// r_m4 image of R (kernels.hip k_amg_restrict)
+// r_m4 image of R (amg.hip k_amg_restrict; built on the host, amg_device.cpp)
 void build_r_m4(const std::vector<uint32_t>& r_row, const std::vector<uint32_t>& r_col, std::vector<int32_t>& out);
 
 // Levels handled by the single-workgroup V-cycle tail kernel.
@@ -315,7 +315,8 @@ struct TailBlobLevel {
   uint32_t maxlen;  // longest row (off-diagonal entries)
 };
 
-// ---------------- launch wrappers (kernels.hip) ----------------
+// ---------------- launch wrappers (one .hip per solver stage) ----------------
+// ---- flux.hip ----
 void launch_prepare(const PrepareArgs& a, hipStream_t s);
 // test mode (reference semantics): the reference's racy prepare with its 64-cell
 // workgroups in order, d_p / grad_p in place (a.dp_out / a.gp_out = a.st's),
@@ -327,6 +328,7 @@ void launch_assemble(const AssembleArgs& a, hipStream_t s);
 // (and to host_out[0..1], a device view of pinned host memory, when non-null)
 void launch_update_fields(uint32_t N, float alpha_u, float alpha_p, const float* x, float2* u,
                           float* p, uint32_t* blockmax, uint32_t* maxbits, uint32_t* host_out, hipStream_t s);
+// ---- krylov.hip ----
 // unit partials (U chunks of 256 cells each) of dot(x, y) over 3-component cells
 void launch_dot_partial(const float* x, const float* y, uint32_t N, uint32_t U, float* partial, hipStream_t s);
 // Reference reduction order (test mode): partial[g] = the 64-wide halving tree
@@ -342,10 +344,12 @@ void launch_ref_cgs_dots(const float* w, const float* basis, const float* binv, 
 // g0 (mode 2): g0[0] = norm, g0[1..g_len) = 0; host_out (device view of pinned host memory, or null) = norm
 void launch_reduce_final(const RedSrc& r, int mode, float* out, float* inv, float* g0, int g_len, float* host_out,
                          hipStream_t s);
+// ---- coupled_rows.hip ----
 // b != null: y = b - A x with the residual axpby's operations (1 * b + -1 * (A x))
-// nt: the matrix and b are read with the nontemporal policy (kernels.hip ldx)
+// nt: the matrix and b are read with the nontemporal policy (device_util.hpp ldx)
 void launch_spmv(const CoupledMatrix& A, const float* x, float* y, hipStream_t s, const float* b = nullptr,
                  bool nt = false);
+// ---- krylov.hip ----
 // basis: unnormalised W_i at basis + i*stride, scales binv[i]; unit partials
 // partial[ii * np + k] of <w, V_ii>, ii = 0..j
 // keep_bytes > 0: the last blocks (their j + 2 vectors within keep_bytes) read
@@ -365,11 +369,14 @@ void launch_cgs_update_norm(const float* w, float* basis, const float* binv, siz
 // small meshes (<= CFD_CGS_LAT_MAX_CELLS): the CGS dots / update in their
 // latency form (several basis vectors per load round trip; same bits)
 bool cgs_latency_form(uint32_t N);
+// large meshes (>= CFD_CGS_SER_MIN_CELLS): the CGS kernels keep one basis load in flight per wavefront
+bool cgs_serial_form(uint32_t N);
 bool cgs_reduce_fusable(const RedSrc& r);
 // ||W_{j+1}|| = sqrt(total of r) -> H[j+1,j], binv[j+1]; Givens update of column j; resid_hist[j] = |g[j+1]|,
 // also into host_resid[j] (device view of pinned host memory) when non-null
 void launch_norm_givens(const RedSrc& r, int j, float* H, int m1, float* givens, float* g, float* binv,
                         float* resid_hist, float* host_resid, hipStream_t s);
+// ---- coupled_rows.hip ----
 // r_in = binv[j] * W_j
 void launch_precond_predict(const CoupledMatrix& A, const float* w_in, const float* binv, int j,
                             const float* dinv_uv, const float* dinv_p, float* temp_p, float* p_sol,
@@ -388,11 +395,13 @@ bool launch_relax_pressure_fused(uint32_t N, uint32_t ld, uint32_t ws, const int
                                  float* temp, uint32_t iters, hipStream_t s);
 void launch_precond_correct(const CoupledMatrix& A, const float* w_in, const float* binv, int j,
                             const float* p_sol, const float* dinv_uv, float* z, hipStream_t s);
+// ---- krylov.hip ----
 void launch_solve_triangular(const float* H, const float* g, float* y, int k, int m1,
                              hipStream_t s);
 // lat: the latency form allowed (small meshes; false = the streaming form)
 void launch_update_x(float* x, const float* z, size_t stride, const float* y, int k, size_t n,
                      hipStream_t s, bool lat = true);
+// ---- amg.hip ----
 // ev0/ev1 (optional): timing events recorded by the GPU at kernel start / end
 // nt: the level matrix, b and the diagonal read with the nontemporal policy
 void launch_amg_smooth(const AmgLevelDev& L, const float* x, const float* b, float* x_out,
@@ -419,6 +428,7 @@ void launch_amg_restrict(const AmgLevelDev& L, const float* r, float* coarse_b, 
                          uint32_t stride_c, uint32_t glo, uint32_t ghi, hipStream_t s,
                          float* sm_out = nullptr, const float* sm_de = nullptr, uint32_t I0 = 0,
                          uint32_t I1 = 0, bool ghosts = true);
+// ---- amg_tail.hip ----
 // V-cycle restricted to levels [first, nlev) of `tail` (device array), one workgroup:
 // pre-smooth / residual / restrict+clear down, 10 coarsest sweeps, prolong / post-smooth up.
 // Every level's x ends in tail[l].x (even sweep counts).
@@ -431,6 +441,7 @@ void launch_amg_tail(const AmgTailLevel* tail, int first, int nlev, size_t lds_b
 void launch_amg_tail_blob(const AmgTailLevel* tail, const TailBlobLevel* desc, const uint32_t* blob,
                           uint32_t blob_words, uint32_t vec_floats, int first, int nlev, const float* b_first,
                           uint32_t n_first, hipStream_t s);
+// ---- amg.hip ----
 // fine rows [f0, f1) (multiples of 4 but f1 = L.n; f1 = 0: all)
 // residual + restriction fused (k_amg_resrestrict; L.rr_agg > 0, replicated
 // or single-GPU level): coarse_b = R (b - A x), coarse_x cleared or the
@@ -452,17 +463,19 @@ void launch_amg_resrestrict_pair(const AmgLevelDev& Lf, const AmgLevelDev& Lm, c
                                  float* sm_out, const float* sm_de, hipStream_t s);
 void launch_amg_prolong(const AmgLevelDev& L, float* x, const float* coarse_x, hipStream_t s, uint32_t f0 = 0,
                         uint32_t f1 = 0, bool nt = false);
+// ---- amg_tail.hip ----
 // Sets the tail kernels' dynamic-LDS attribute on `device` (once per device,
 // thread-safe; throws on failure) and returns their LDS budget there:
 // min(kTailLdsMax, the device's opt-in per-block LDS).  Call with `device` current.
 size_t init_kernel_attributes(int device);
+// ---- stats_dist.hip ----
 // check_evolution (coupled_solver.rs:501-580) statistics in the canonical order (f64):
 // chunk partials partial[f * np + k], f = {evolution, sum_u, sum_v, sumsq_u, sumsq_v}
 // The variance part reads record ((gbase + c) >> 2) - rec0 of `var` (stride bug, §0.1-12).
 void launch_evolution_partial(StateView cur, StateView prev, int have_prev, uint32_t N,
                               StateView var, uint64_t gbase, uint64_t rec0, uint32_t U, double* partial, uint32_t np,
                               hipStream_t s);
-// ---- distributed helpers ----
+// distributed helpers
 void launch_pack(const PackArgs& a, hipStream_t s);
 // distributed: this rank's segment values out[v * maxseg + s] of nvec reductions
 // from their unit partials part[v * np + k] (k < nunits local, G units per segment)
@@ -474,7 +487,7 @@ void launch_max_combine(const uint32_t* gathered, int R, uint32_t* out, uint32_t
 // out[f] = total of vector f of r, f < r.nvec (check_evolution: 5 sums; flow diagnostics: 6)
 void launch_evolution_final(const RedSrcD& r, double* out, hipStream_t s);
 
-// ---- flow diagnostics (diagnostics.hip) ----
+// ---- diagnostics.hip: flow diagnostics ----
 // One read-only sweep over the owned cells of a state: Green-Gauss gradients of
 // u as k_prepare forms them (the same bits), omega = dv/dx - du/dy and div =
 // du/dx + dv/dy per cell, and per cell the f64 terms (each evaluated left to

@@ -72,6 +72,16 @@ struct DevTmp {
 
 }  // namespace
 
+void build_r_m4(const std::vector<uint32_t>& r_row, const std::vector<uint32_t>& r_col, std::vector<int32_t>& out) {
+  const size_t nc = r_row.empty() ? 0 : r_row.size() - 1;
+  out.assign(4 * nc, -1);
+  for (size_t I = 0; I < nc; ++I) {
+    const uint32_t k0 = r_row[I], m = r_row[I + 1] - k0;
+    for (uint32_t q = 0; q < m && q < 4; ++q) out[4 * I + q] = (int32_t)r_col[k0 + q];
+    if (m > 4) out[4 * I + 3] = -2 - (int32_t)r_col[k0 + 3];  // overflow flag; member 3 = -2 - w
+  }
+}
+
 // a level as the setup sees it: pattern on the host, values on the device
 struct AmgSetupLevel {
   uint32_t n = 0;                  // rows

@@ -3,7 +3,7 @@
 //   coupled_solver_fgmres.rs:1728-2448  solve_coupled_fgmres (FGMRES(50) + Schur)
 //   linear_solver/amg.rs:666-770        v_cycle (amg_cycle.cpp)
 //   solver.rs:9-44, 97-128, 276-294     set_u / set_p / set_dt / getters / history
-// over the kernels of ../hip/kernels.hip, on one HIP stream.  All vectors stay
+// over the kernels of ../hip/*.hip, on one HIP stream.  All vectors stay
 // in HBM; host round trips are the ones the reference control flow needs
 // (blocking norms at solve start / restart, lagged residual reads), and none
 // under the fixed benchmark schedule except the two early-exit norms.
@@ -96,7 +96,7 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
   // top-down update (profiles/r04/ab_cgskeep2_c1.txt: update 36.5-36.9 ->
   // 32.3 us, dots +0.3 us per iteration); from 2^22 cells on the kept lines
   // cost more than they return (ab_cgskeep_c2.txt: dots 284 -> 293 us)
-  cgs_keep_bytes = N < (1u << 22) ? (size_t)64 << 20 : 0;  // (kernels.hip CFD_CGS_SER_MIN_CELLS)
+  cgs_keep_bytes = !cgs_serial_form(N) ? (size_t)64 << 20 : 0;
   CFD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   amg_local = dist() && cfg.amg_local_aggregation != 0;
   // hipGraph replay: opt-in through cfd_graph_enable (replay measured no faster
@@ -699,7 +699,7 @@ void level_image(const HostCsr& A, uint64_t r0, uint32_t n, Rel rel, AmgGpuLevel
 // (the one a single GPU builds, so results do not depend on the rank count)
 // and keeps its rows of the levels with more than CFD_AMG_REPLICATE_ROWS rows
 // (default kAmgReplicateRowsDefault); the small levels are replicated on every rank.
-// Unconditional slot loads (kernels.hip gather_group) on level 0 (the face
+// Unconditional slot loads (amg_rows.hpp gather_group) on level 0 (the face
 // stencil: rows fill the ELL width) and on latency-bound small levels;
 // predicated loads on the big coarse levels, whose row lengths vary (same-box
 // A/B at C2: level 1 smoother 58 vs 66 us, small-level residual 6 vs 8.5 us).

@@ -433,7 +433,7 @@ struct Solver {
   // the update kernel (<= 256 reduction units), every Jacobi relaxation sweep
   // in one single-workgroup launch (<= 8191 cells)
   bool small_forms = true;
-  // nontemporal loads of the matrix streams (kernels.hip ldx), per kernel, for
+  // nontemporal loads of the matrix streams (device_util.hpp ldx), per kernel, for
   // the last readers of a matrix before the cycle moves on (CFD_NT, bit mask):
   // 1 post-smoother of the split levels, 2 level-0 AMG residual, 4 Schur
   // prediction, 8 SpMV, 16 pre-smoother, 32 the prolongation map of the split

@@ -1,4 +1,4 @@
-"""Build kernel variants (compile-time tunables of kernels.hip) as separate
+"""Build kernel variants (compile-time tunables of csrc/hip/*.hip) as separate
 libraries for same-box A/B timing:  python tools/ab_variants.py NAME=DEF,DEF ...
 e.g.  u1=CFD_SPMV_U=1  u2=CFD_SPMV_U=2,CFD_PREDICT_U=2
 Libraries land in cfd-demo2_amd/cfd2_amd/_lib/variants/; select one at run
