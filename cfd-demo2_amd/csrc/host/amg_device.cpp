@@ -12,7 +12,8 @@
 //          the V-cycle layout (AmgLevelDev)
 //   host   download of the coarse pattern (the next aggregation's input)
 // Level 0 is read straight from the assembled ELL scalar matrix.  The result
-// is bit-identical to the host path (tests/test_gpu_parity.py compares both);
+// is bit-identical to the host path (tests/test_gpu_parity.py compares both):
+// every path lays its levels out through the same functions (amg_levels.cpp);
 // should a coarse row exceed the kernel's per-thread capacities, or a level
 // need the wide-row layout, the host path runs instead.
 //
@@ -47,28 +48,6 @@ namespace cfd2 {
 namespace {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// temporary device buffer (setup scratch; the arena holds what the V-cycle keeps)
-template <class T>
-struct DevTmp {
-  T* p = nullptr;
-  DevTmp() = default;
-  explicit DevTmp(size_t n) { CFD_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T))); }
-  DevTmp(const DevTmp&) = delete;
-  DevTmp& operator=(const DevTmp&) = delete;
-  DevTmp(DevTmp&& o) noexcept : p(o.p) { o.p = nullptr; }
-  DevTmp& operator=(DevTmp&& o) noexcept {
-    if (this != &o) {
-      if (p) (void)hipFree(p);
-      p = o.p;
-      o.p = nullptr;
-    }
-    return *this;
-  }
-  ~DevTmp() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 }  // namespace
 
@@ -124,11 +103,6 @@ bool Solver::device_levels(AmgSetupLevel& cur_in, int li0, const std::vector<uin
   const bool timing = cfg.log_level >= 2 && rk == 0;
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
-  auto zeroed = [&](size_t cnt) {
-    float* p = arena.alloc<float>(cnt + 64);
-    CFD_HIP(hipMemsetAsync(p, 0, (cnt + 64) * sizeof(float), stream));
-    return p;
-  };
   AmgSetupLevel cur = std::move(cur_in);  // (a moved vector keeps its buffer: row / col stay valid)
   for (int li = li0; li < kMaxAmgLevels; ++li) {
     const auto t0 = clk::now();
@@ -145,63 +119,19 @@ bool Solver::device_levels(AmgSetupLevel& cur_in, int li0, const std::vector<uin
       G.C0 = 0;
       G.C1 = n;
     }
-    // ---- level image (same bytes as the host level_image)
-    int wmax = 0;
-    bool small_delta = true;
-    const uint32_t* crow = cur.row;
-    const uint32_t* ccol = cur.col;
-#pragma omp parallel for reduction(max : wmax) reduction(&& : small_delta) schedule(static)
-    for (long ii = 0; ii < (long)n; ++ii) {
-      const uint32_t i = (uint32_t)ii;
-      int off = 0;
-      for (uint32_t k = crow[i]; k < crow[i + 1]; ++k) {
-        const int64_t c = (int64_t)ccol[k];
-        if (c == (int64_t)i) continue;
-        ++off;
-        const int64_t d = c - (int64_t)i;
-        if (d < -32768 || d > 32767) small_delta = false;
-      }
-      wmax = std::max(wmax, off);
-    }
+    // ---- level image (global numbering: the columns are local already)
+    const LevelShape shape = level_shape(cur.row, cur.col, n, 0, nullptr);
     // a row wider than the u8 layout: the host path builds that level with 16-bit lengths
-    if (wmax > amg_wide_limit) {
+    if (shape.wmax > amg_wide_limit) {
       if (timing) std::fprintf(stderr, "[amg setup] device path: wide rows at level %d, host path\n", li);
       return false;
     }
-    const uint32_t st = (n + 63) & ~63u;
-    const size_t slots = (size_t)std::max(wmax, 1) * st;
-    G.nnz = cur.row[n] - cur.row[0];
-    G.dev.n = n;
-    G.dev.r0 = 0;
-    G.dev.r1 = n;
-    G.dev.stride = st;
-    G.dev.w = wmax;
-    G.dev.use16 = small_delta ? 1 : 0;
-    float* val = arena.alloc<float>(slots);
-    int16_t* col16 = small_delta ? arena.alloc<int16_t>(slots) : nullptr;
-    int32_t* col32 = small_delta ? nullptr : arena.alloc<int32_t>(slots);
-    uint8_t* len = arena.alloc<uint8_t>(st);
-    uint8_t* drank = arena.alloc<uint8_t>(st);
-    float* dv = arena.alloc<float>(st);
-    float* de = arena.alloc<float>(st);
-    launch_amg_pack(cur.dev, n, st, wmax, G.dev.use16, val, col16, col32, len, drank, dv, de, stream);
-    CFD_HIP(hipGetLastError());
-    G.dev.val = val;
-    G.dev.col16 = col16;
-    G.dev.col32 = col32;
-    G.dev.len = len;
-    G.dev.drank = drank;
-    G.dev.dv = dv;
-    G.dev.de = de;
+    set_level_header(G, n, (n + 63) & ~63u, shape, cur.row[n] - cur.row[0]);
+    alloc_level_image(G);
+    pack_level(cur.dev, G);
     amg_refresh.emplace_back();
     amg_refresh.back().fine = cur.dev;
-    G.npad = st;
-    G.xt = zeroed(st);
-    G.r = zeroed(st);
-    if (li > 0) {
-      G.x = zeroed(st);
-      G.b = zeroed(st);
-    }
+    alloc_level_vectors(G, li);
     set_amg_full_policy(G, li);
     // ---- coarsening (amg.rs:374-595: stop at n <= 100, no reduction or the level cap)
     if (!(li < kMaxAmgLevels - 1 && n > 100)) break;
@@ -211,36 +141,15 @@ bool Solver::device_levels(AmgSetupLevel& cur_in, int li0, const std::vector<uin
     if (nagg >= n) break;
     transpose_aggregates(agg, nagg, r_row, r_col);
     const double t_agg = secs(t0);
-    std::vector<uint32_t> aggp(st, 0);
-    for (uint32_t i = 0; i < n; ++i) aggp[i] = agg[i];
-    G.dev.agg = arena.upload(aggp, stream, kAggSlack);
-    G.dev.r_row = arena.upload(r_row, stream);
-    G.dev.r_col = arena.upload(r_col, stream);
-    {
-      std::vector<int32_t> m4;
-      build_r_m4(r_row, r_col, m4);
-      G.dev.r_m4 = reinterpret_cast<const int4*>(arena.upload(m4, stream));
-    }
-    G.dev.nc = nagg;
+    upload_transfer(G, agg, r_row, r_col);
     const uint32_t* gal_agg = G.dev.agg;  // Galerkin columns: aggregate id of every fine column
-    // ---- Galerkin product on the device
+    // ---- Galerkin product on the device (every rank computes the same flag: no collective)
     AmgSetupLevel next;
     next.n = nagg;
-    DevTmp<uint32_t> d_cnt(nagg);
-    launch_galerkin(cur.dev, gal_agg, G.dev.r_row, G.dev.r_col, nagg, d_cnt.p, nullptr, nullptr, nullptr,
-                    amg_setup_flag, stream);
-    CFD_HIP(hipGetLastError());
-    next.own_row.assign((size_t)nagg + 1, 0);
-    uint32_t flag = 0;
-    CFD_HIP(hipMemcpyAsync(next.own_row.data() + 1, d_cnt.p, (size_t)nagg * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, stream));
-    CFD_HIP(hipMemcpyAsync(&flag, amg_setup_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    sync();
-    if (flag != 0) {
+    if (!galerkin_count(cur.dev, gal_agg, G.dev.r_row, G.dev.r_col, nagg, false, next.own_row)) {
       if (timing) std::fprintf(stderr, "[amg setup] device path: capacity overflow at level %d\n", li);
       return false;
     }
-    for (uint32_t I = 0; I < nagg; ++I) next.own_row[I + 1] += next.own_row[I];
     const size_t nnz_c = next.own_row[nagg];
     next.d_rowptr = arena.alloc<uint32_t>((size_t)nagg + 1);
     next.d_col = arena.alloc<int32_t>(nnz_c);
@@ -313,17 +222,6 @@ bool Solver::build_amg_device_dist() {
   amg_g = 0;
   amg_setup_flag = arena.alloc<uint32_t>(1);
   CFD_HIP(hipMemsetAsync(amg_setup_flag, 0, sizeof(uint32_t), stream));
-  auto zeroed = [&](size_t cnt) {
-    float* p = arena.alloc<float>(cnt + 64);
-    CFD_HIP(hipMemsetAsync(p, 0, (cnt + 64) * sizeof(float), stream));
-    return p;
-  };
-  auto any_rank = [&](bool mine) {
-    for (uint64_t f : allgather_u64(mine ? 1 : 0))
-      if (f) return true;
-    return false;
-  };
-
   // the current (row-partitioned) level: own rows' pattern with global
   // columns on the host, values on the device (level 0: the ELL scalar matrix)
   struct DLevel {
@@ -354,6 +252,7 @@ bool Solver::build_amg_device_dist() {
     const uint64_t C0 = cur.C0, C1 = cur.C1;
     const uint32_t n = (uint32_t)(C1 - C0);
     const std::vector<uint32_t>& gh = cur.ghost;
+    const RowWindow win(C0, C1, gh, cur.glo);
     levels.emplace_back();
     AmgGpuLevel& G = levels.back();
     G.dist = true;
@@ -361,18 +260,9 @@ bool Solver::build_amg_device_dist() {
     G.part = cur.part;
     G.C0 = C0;
     G.C1 = C1;
-    G.glo = cur.glo;
-    G.ghi = (uint32_t)gh.size() - cur.glo;
-    G.npad = (n + 63) & ~63u;
-    if (li == 0 && (G.glo != topo.glo || G.ghi != topo.ghi || G.npad != topo.npad))
-      throw std::logic_error("AMG level 0 ghosts differ from the cell ghosts");
-    auto rel = [&](uint32_t c) -> int32_t {  // signed local index of an owned row or ghost of this level
-      if (c >= C0 && c < C1) return (int32_t)(c - C0);
-      const auto it = std::lower_bound(gh.begin(), gh.end(), c);
-      if (it == gh.end() || *it != c) throw std::logic_error("AMG: row is neither owned nor a ghost");
-      const uint32_t k = (uint32_t)(it - gh.begin());
-      return k < G.glo ? (int32_t)k - (int32_t)G.glo : (int32_t)(G.npad + (k - G.glo));
-    };
+    G.glo = win.glo;
+    G.ghi = win.ghi();
+    G.npad = win.npad;
     // ---- halo plan of the level (every rank's ghost list)
     {
       const auto ghosts_all = allgatherv_u32(gh);
@@ -383,77 +273,30 @@ bool Solver::build_amg_device_dist() {
     // ---- level image from the local-column view of the level
     const uint32_t* row = cur.row;
     const uint32_t* col = cur.col;
-    int wmax = 0;
-    bool small_delta = true;
-    std::vector<int32_t> lcol;
-    if (!cur.ell) lcol.resize(row[n] - row[0]);
-    for (uint32_t i = 0; i < n; ++i) {
-      int off = 0;
-      for (uint32_t k = row[i]; k < row[i + 1]; ++k) {
-        const int32_t c = cur.ell ? 0 : rel(col[k]);
-        if (!cur.ell) lcol[k - row[0]] = c;
-        if (col[k] == C0 + i) continue;
-        ++off;
-        const int64_t d = (int64_t)(cur.ell ? rel(col[k]) : c) - (int64_t)i;
-        if (d < -32768 || d > 32767) small_delta = false;
-      }
-      wmax = std::max(wmax, off);
-    }
-    if (any_rank(wmax > amg_wide_limit)) {  // the host path handles (or rejects) wide rows
+    const LevelShape shape = level_shape(row, col, n, C0, &win);
+    if (any_rank(shape.wmax > amg_wide_limit)) {  // the host path handles (or rejects) wide rows
       if (timing) std::fprintf(stderr, "[amg setup] device path: wide rows at level %d, host path\n", li);
       return false;
     }
     SetupMatrix src{};
+    src.val = cur.val;
+    std::vector<int32_t> lcol;
     if (cur.ell) {
       src.ell = 1;
       src.ld = topo.ld;
       src.len = d_slen;
       src.col = d_scol;  // signed local columns
-      src.val = cur.val;
     } else {
+      lcol.resize(row[n] - row[0]);
+      for (uint32_t k = row[0]; k < row[n]; ++k) lcol[k - row[0]] = win.rel(col[k]);
       src.ell = 0;
       src.rowptr = cur.d_rowptr;
       src.col = arena.upload(lcol, stream);
-      src.val = cur.val;
     }
-    {
-      const uint32_t st = G.npad;
-      const size_t slots = (size_t)std::max(wmax, 1) * st;
-      G.nnz = row[n] - row[0];
-      G.dev.n = n;
-      G.dev.r0 = 0;
-      G.dev.r1 = n;
-      G.dev.stride = st;
-      G.dev.w = wmax;
-      G.dev.use16 = small_delta ? 1 : 0;
-      float* val = arena.alloc<float>(slots);
-      int16_t* col16 = small_delta ? arena.alloc<int16_t>(slots) : nullptr;
-      int32_t* col32 = small_delta ? nullptr : arena.alloc<int32_t>(slots);
-      uint8_t* len = arena.alloc<uint8_t>(st);
-      uint8_t* drank = arena.alloc<uint8_t>(st);
-      float* dv = arena.alloc<float>(st);
-      float* de = arena.alloc<float>(st);
-      launch_amg_pack(src, n, st, wmax, G.dev.use16, val, col16, col32, len, drank, dv, de, stream);
-      CFD_HIP(hipGetLastError());
-      G.dev.val = val;
-      G.dev.col16 = col16;
-      G.dev.col32 = col32;
-      G.dev.len = len;
-      G.dev.drank = drank;
-      G.dev.dv = dv;
-      G.dev.de = de;
-    }
-    if (li == 0) {
-      G.xt = valloc<float>(1);
-      G.r = valloc<float>(1);
-    } else {
-      const uint32_t sh = (G.glo + 63) & ~63u;
-      const size_t cnt = (size_t)sh + G.npad + G.ghi;
-      G.x = zeroed(cnt) + sh;
-      G.xt = zeroed(cnt) + sh;
-      G.b = zeroed(cnt) + sh;
-      G.r = zeroed(cnt) + sh;
-    }
+    set_level_header(G, n, win.npad, shape, row[n] - row[0]);
+    alloc_level_image(G);
+    pack_level(src, G);
+    alloc_level_vectors(G, li);
     set_amg_full_policy(G, li);
     amg_refresh.emplace_back();
     amg_refresh.back().fine = src;
@@ -679,24 +522,12 @@ bool Solver::build_amg_device_dist() {
     F.r_col = arena.upload(m_rcol, stream);
     F.nagg_own = nown_c;
     member_values(F);
-    // Galerkin count pass
-    std::vector<uint32_t> crow(nown_c + 1, 0);
-    uint32_t flag = 0;
-    {
-      DevTmp<uint32_t> d_cnt(nown_c);
-      launch_galerkin(F.mem, nullptr, F.r_row, F.r_col, nown_c, d_cnt.p, nullptr, nullptr, nullptr, amg_setup_flag,
-                      stream);
-      CFD_HIP(hipGetLastError());
-      if (nown_c)
-        CFD_HIP(hipMemcpyAsync(crow.data() + 1, d_cnt.p, (size_t)nown_c * 4, hipMemcpyDeviceToHost, stream));
-      CFD_HIP(hipMemcpyAsync(&flag, amg_setup_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-      sync();
-    }
-    if (any_rank(flag != 0)) {
+    // Galerkin count pass (the overflow decision is collective)
+    std::vector<uint32_t> crow;
+    if (!galerkin_count(F.mem, nullptr, F.r_row, F.r_col, nown_c, true, crow)) {
       if (timing) std::fprintf(stderr, "[amg setup] device path: capacity overflow at level %d\n", li);
       return false;
     }
-    for (uint32_t I = 0; I < nown_c; ++I) crow[I + 1] += crow[I];
     const size_t nnz_c = crow[nown_c];
     uint32_t* d_crow = arena.upload(crow, stream);
     // fill: into this rank's coarse rows, or straight into the all-gathered
@@ -728,58 +559,23 @@ bool Solver::build_amg_device_dist() {
 
     // ---- next level's ghosts (distributed next level)
     std::vector<uint32_t> ngh;
-    uint32_t nglo = 0;
-    const uint32_t nnpad = (nown_c + 63) & ~63u;
-    if (next_dist) {
-      for (uint32_t c : ccol)
-        if (c < I0 || c >= I1) ngh.push_back(c);
-      for (uint32_t a : agg)
-        if (a < I0 || a >= I1) ngh.push_back(a);
-      std::sort(ngh.begin(), ngh.end());
-      ngh.erase(std::unique(ngh.begin(), ngh.end()), ngh.end());
-      nglo = (uint32_t)(std::lower_bound(ngh.begin(), ngh.end(), (uint32_t)I0) - ngh.begin());
-    }
-    auto rel_next = [&](uint32_t c) -> int32_t {
-      if (c >= I0 && c < I1) return (int32_t)(c - I0);
-      const auto it = std::lower_bound(ngh.begin(), ngh.end(), c);
-      if (it == ngh.end() || *it != c) throw std::logic_error("AMG: coarse row is neither owned nor a ghost");
-      const uint32_t k = (uint32_t)(it - ngh.begin());
-      return k < nglo ? (int32_t)k - (int32_t)nglo : (int32_t)(nnpad + (k - nglo));
-    };
-    // ---- P and R of this level in the V-cycle layout (as build_amg_host)
+    const uint32_t nglo =
+        next_dist ? level_ghosts(I0, I1, crow.data(), nown_c, ccol.data(), agg.data(), agg.size(), ngh) : 0;
+    const RowWindow nwin(I0, I1, ngh, nglo);
+    // ---- P and R of this level in the V-cycle layout
     {
-      std::vector<uint32_t> aggp(G.dev.stride, 0), r_row(nown_c + 1), r_col(m_rcol.size());
-      for (uint32_t i = 0; i < n; ++i) aggp[i] = next_dist ? (uint32_t)rel_next(agg[i]) : agg[i];
-      for (uint32_t I = 0; I <= nown_c; ++I) r_row[I] = m_rrow[I];
+      std::vector<uint32_t> aggl(n), r_col(m_rcol.size());
+      for (uint32_t i = 0; i < n; ++i) aggl[i] = next_dist ? (uint32_t)nwin.rel(agg[i]) : agg[i];
       for (size_t k = 0; k < m_rcol.size(); ++k) {
         const uint32_t t = m_rcol[k];
-        const int32_t lf = t < n ? (int32_t)t : rel(imp[t - n]);
+        const int32_t lf = t < n ? (int32_t)t : win.rel(imp[t - n]);
         if (lf < 0) throw std::logic_error("AMG: aggregate member below its seed's rank");
         r_col[k] = (uint32_t)lf;
       }
-      G.dev.nc = nown_c;
-      const uint32_t nown = n;
-      G.rc_hi = nown_c;
-      for (uint32_t I = 0; I < nown_c; ++I) {
-        bool ghost = false;
-        for (uint32_t k = r_row[I]; k < r_row[I + 1]; ++k) ghost |= r_col[k] >= nown;
-        if (ghost) {
-          G.rc_hi = I;
-          break;
-        }
-      }
-      G.pf_lo = 0;
-      if (next_dist) {
-        for (uint32_t i = 0; i < nown; ++i)
-          if ((int32_t)aggp[i] < 0 || aggp[i] >= nown_c) G.pf_lo = i + 1;
-        G.pf_lo = std::min((G.pf_lo + 3) & ~3u, nown);
-      }
-      G.dev.agg = arena.upload(aggp, stream, kAggSlack);
-      G.dev.r_row = arena.upload(r_row, stream);
-      G.dev.r_col = arena.upload(r_col, stream);
-      std::vector<int32_t> m4;
-      build_r_m4(r_row, r_col, m4);
-      G.dev.r_m4 = reinterpret_cast<const int4*>(arena.upload(m4, stream));
+      const TransferBounds tb = transfer_bounds(m_rrow, r_col, aggl, n, nown_c, next_dist);
+      G.rc_hi = tb.rc_hi;
+      G.pf_lo = tb.pf_lo;
+      upload_transfer(G, aggl, m_rrow, r_col);
     }
     if (timing)
       std::fprintf(stderr,
@@ -872,10 +668,7 @@ void Solver::refresh_amg() {
   CFD_HIP(hipMemcpyAsync(amg_src, sval, slots_s * sizeof(float), hipMemcpyDeviceToDevice, stream));
   for (size_t li = 0; li < amg_refresh.size(); ++li) {
     const AmgRefreshLevel& F = amg_refresh[li];
-    const AmgLevelDev& d = levels[li].dev;
-    launch_amg_pack(F.fine, d.n, d.stride, d.w, d.use16, const_cast<float*>(d.val), const_cast<int16_t*>(d.col16),
-                    const_cast<int32_t*>(d.col32), const_cast<uint8_t*>(d.len), const_cast<uint8_t*>(d.drank),
-                    const_cast<float*>(d.dv), const_cast<float*>(d.de), stream);
+    pack_level(F.fine, levels[li]);
     if (!F.has_coarse) continue;
     if (F.dist) {
       member_values(F);

@@ -129,6 +129,21 @@ void transpose_aggregates(const std::vector<uint32_t>& agg, uint32_t nagg, std::
   for (size_t i = 0; i < n; ++i) r_col[pos[agg[i]]++] = (uint32_t)i;  // ascending i
 }
 
+TransferBounds transfer_bounds(const std::vector<uint32_t>& r_row, const std::vector<uint32_t>& r_col,
+                               const std::vector<uint32_t>& agg, uint32_t nown, uint32_t nc, bool next_dist) {
+  TransferBounds t;
+  t.rc_hi = nc;
+  for (uint32_t I = 0; I < nc && t.rc_hi == nc; ++I)
+    for (uint32_t k = r_row[I]; k < r_row[I + 1]; ++k)
+      if (r_col[k] >= nown) t.rc_hi = I;
+  if (next_dist) {
+    for (uint32_t i = 0; i < nown; ++i)
+      if ((int32_t)agg[i] < 0 || agg[i] >= nc) t.pf_lo = i + 1;
+    t.pf_lo = std::min((t.pf_lo + 3) & ~3u, nown);
+  }
+  return t;
+}
+
 std::vector<AmgHostLevel> build_amg_hierarchy(const HostCsr& fine, size_t max_levels,
                                                const std::vector<uint64_t>& part0, bool local, uint64_t rep_rows,
                                                bool timing) {

@@ -29,14 +29,73 @@ int owner_of(const std::vector<uint64_t>& starts, uint64_t g) {
   return (int)(std::upper_bound(starts.begin(), starts.end(), g) - starts.begin()) - 1;
 }
 
-uint32_t collect_ghosts(uint64_t c0, uint64_t c1, const uint32_t* row, uint32_t n, const uint32_t* col,
-                        std::vector<uint32_t>& ghost) {
+bool RowWindow::find(uint64_t g, int32_t& local) const {
+  if (g >= c0 && g < c1) {
+    local = (int32_t)(g - c0);
+    return true;
+  }
+  const uint32_t* it = std::lower_bound(ghost, ghost + nghost, g);
+  if (it == ghost + nghost || *it != g) return false;
+  const uint32_t k = (uint32_t)(it - ghost);
+  local = k < glo ? (int32_t)k - (int32_t)glo : (int32_t)(npad + (k - glo));
+  return true;
+}
+
+int32_t RowWindow::rel(uint64_t g) const {
+  int32_t local = 0;
+  if (!find(g, local)) throw std::logic_error("row " + std::to_string(g) + " is neither owned nor a ghost");
+  return local;
+}
+
+uint32_t level_ghosts(uint64_t c0, uint64_t c1, const uint32_t* row, uint32_t n, const uint32_t* col,
+                      const uint32_t* extra, size_t nextra, std::vector<uint32_t>& ghost) {
   ghost.clear();
   for (uint64_t k = row[0]; k < row[n]; ++k)
     if (col[k] < c0 || col[k] >= c1) ghost.push_back(col[k]);
+  for (size_t k = 0; k < nextra; ++k)
+    if (extra[k] < c0 || extra[k] >= c1) ghost.push_back(extra[k]);
   std::sort(ghost.begin(), ghost.end());
   ghost.erase(std::unique(ghost.begin(), ghost.end()), ghost.end());
   return (uint32_t)(std::lower_bound(ghost.begin(), ghost.end(), (uint32_t)c0) - ghost.begin());
+}
+
+namespace {
+// local(c, l): the local index of global column c; false when it has none
+// (no exception may leave the parallel loop: the caller reports it)
+template <class Local>
+LevelShape shape_scan(const uint32_t* row, const uint32_t* col, uint32_t n, uint64_t g0, bool& known_out,
+                      Local local) {
+  int wmax = 0;
+  bool small_delta = true, known = true;
+#pragma omp parallel for reduction(max : wmax) reduction(&& : small_delta, known) schedule(static)
+  for (long ii = 0; ii < (long)n; ++ii) {
+    int off = 0;
+    for (uint32_t k = row[ii]; k < row[ii + 1]; ++k) {
+      if (col[k] == g0 + (uint64_t)ii) continue;
+      ++off;
+      int32_t l = 0;
+      if (!local(col[k], l)) known = false;
+      const int64_t d = (int64_t)l - (int64_t)ii;
+      if (d < -32768 || d > 32767) small_delta = false;
+    }
+    wmax = std::max(wmax, off);
+  }
+  known_out = known;
+  return {wmax, small_delta};
+}
+}  // namespace
+
+LevelShape level_shape(const uint32_t* row, const uint32_t* col, uint32_t n, uint64_t g0, const RowWindow* win) {
+  bool known = true;
+  if (!win)
+    return shape_scan(row, col, n, g0, known, [](uint32_t c, int32_t& l) {
+      l = (int32_t)c;
+      return true;
+    });
+  const LevelShape s = shape_scan(row, col, n, g0, known, [win](uint32_t c, int32_t& l) { return win->find(c, l); });
+  if (!known)  // rel throws at the first column outside the window
+    for (uint64_t k = row[0]; k < row[n]; ++k) (void)win->rel(col[k]);
+  return s;
 }
 
 void interior_rows(const std::vector<uint64_t>& starts, int rank, const uint32_t* row, uint32_t n,

@@ -604,105 +604,6 @@ void Solver::ensure_fgmres() {  // coupled_solver_fgmres.rs:212-1280 (lazy)
   fgmres_ready = true;
 }
 
-namespace {
-
-// Device image of rows [r0, r0 + n) of the level matrix A (global numbering),
-// off-diagonal columns mapped to local indices by `rel`; see AmgLevelDev.
-template <class Rel>
-void level_image(const HostCsr& A, uint64_t r0, uint32_t n, Rel rel, AmgGpuLevel& G, DeviceArena& arena,
-                 hipStream_t stream, int wide_limit) {
-  const uint32_t st = (n + 63) & ~63u;  // padded row count (16-byte row groups)
-  int wmax = 0;
-  bool small_delta = true;
-  std::vector<uint8_t> len(st, 0), drank(st, 0);
-  std::vector<uint16_t> len16(st, 0), drank16(st, 0);
-  std::vector<float> dv(st, 0.0f), de(st, 1.0f);
-  uint64_t nnz = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t gi = r0 + i;
-    uint32_t off = 0, dr = 0;
-    bool has = false;
-    float diag = 1.0f, raw = 0.0f;
-    for (uint32_t k = A.row[gi]; k < A.row[gi + 1]; ++k) {
-      const uint32_t c = A.col[k];
-      if (c == gi) {
-        has = true;
-        raw = A.val[k];
-        diag = raw;
-        dr = off;
-      } else {
-        ++off;
-        const int64_t d = (int64_t)rel(c) - (int64_t)i;
-        if (d < -32768 || d > 32767) small_delta = false;
-      }
-    }
-    nnz += A.row[gi + 1] - A.row[gi];
-    if (!has) dr = off;  // no diagonal entry: raw diag contributes nothing (dv = 0)
-    if (std::fabs(diag) < 1e-14f) diag = 1.0f;  // amg.wgsl:46
-    if (off > 65535) throw std::invalid_argument("AMG level row wider than 65535 entries (unsupported)");
-    len[i] = (uint8_t)std::min(off, 255u);
-    drank[i] = (uint8_t)std::min(dr, 255u);
-    len16[i] = (uint16_t)off;
-    drank16[i] = (uint16_t)dr;
-    dv[i] = raw;
-    de[i] = diag;
-    wmax = std::max(wmax, (int)off);
-  }
-  const size_t slots = (size_t)std::max(wmax, 1) * st;
-  std::vector<float> val(slots, 0.0f);
-  std::vector<int16_t> col16(small_delta ? slots : 0, 0);
-  std::vector<int32_t> col32(small_delta ? 0 : slots, 0);
-  for (uint32_t i = 0; i < st; ++i) {
-    uint32_t r = 0;
-    if (i < n) {
-      const uint64_t gi = r0 + i;
-      for (uint32_t k = A.row[gi]; k < A.row[gi + 1]; ++k) {
-        const uint32_t c = A.col[k];
-        if (c == gi) continue;
-        const size_t o = (size_t)r * st + i;
-        val[o] = A.val[k];
-        if (small_delta)
-          col16[o] = (int16_t)((int64_t)rel(c) - (int64_t)i);
-        else
-          col32[o] = rel(c);
-        ++r;
-      }
-    }
-    // padding slots / rows: value 0, column = the row itself (allocated, zeroed)
-    if (!small_delta)
-      for (; r < (uint32_t)std::max(wmax, 1); ++r) col32[(size_t)r * st + i] = (int32_t)i;
-  }
-  G.nnz = nnz;
-  G.dev.n = n;
-  G.dev.r0 = 0;
-  G.dev.r1 = n;
-  G.dev.stride = st;
-  G.dev.w = wmax;
-  G.dev.use16 = small_delta ? 1 : 0;
-  G.dev.val = arena.upload(val, stream);
-  G.dev.col16 = small_delta ? arena.upload(col16, stream) : nullptr;
-  G.dev.col32 = small_delta ? nullptr : arena.upload(col32, stream);
-  G.dev.len = arena.upload(len, stream);
-  G.dev.drank = arena.upload(drank, stream);
-  G.dev.dv = arena.upload(dv, stream);
-  G.dev.de = arena.upload(de, stream);
-  G.wide = wmax > wide_limit;
-  G.dev.len16 = G.wide ? arena.upload(len16, stream) : nullptr;
-  G.dev.drank16 = G.wide ? arena.upload(drank16, stream) : nullptr;
-}
-
-}  // namespace
-
-// ensure_amg_resources (coupled_solver_fgmres.rs:174-209): read back the live
-// scalar matrix, build the frozen hierarchy on the host, upload it.  A
-// distributed rank all-gathers the scalar matrix, builds the GLOBAL hierarchy
-// (the one a single GPU builds, so results do not depend on the rank count)
-// and keeps its rows of the levels with more than CFD_AMG_REPLICATE_ROWS rows
-// (default kAmgReplicateRowsDefault); the small levels are replicated on every rank.
-// Unconditional slot loads (amg_rows.hpp gather_group) on level 0 (the face
-// stencil: rows fill the ELL width) and on latency-bound small levels;
-// predicated loads on the big coarse levels, whose row lengths vary (same-box
-// A/B at C2: level 1 smoother 58 vs 66 us, small-level residual 6 vs 8.5 us).
 std::vector<uint64_t> Solver::allgather_u64(uint64_t mine) {
   std::vector<uint64_t> all(R, mine);
   if (!dist()) return all;
@@ -712,241 +613,6 @@ std::vector<uint64_t> Solver::allgather_u64(uint64_t mine) {
   CFD_HIP(hipMemcpyAsync(all.data(), d_u64 + 1, (size_t)R * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   sync();
   return all;
-}
-
-// Unconditional slot loads + vector gathers (MODE 1) where the rows fill the
-// ELL width (level 0; the first coarse levels of the face-stencil meshes: mean
-// off-diagonal count >= 3/4 of the width; C2 A/B: level-1 smoother 55.0 ->
-// 50.2 us, level 2 15.1 -> 12.3) and on the small latency-bound levels;
-// predicated loads on ragged big levels.
-void Solver::set_amg_full_policy(AmgGpuLevel& G, int li) {
-  const char* fe = knob(Knob::AmgFull);
-  const double n = std::max<double>(G.dev.n, 1.0);
-  const double offd = ((double)G.nnz - n) / n;  // mean off-diagonals per row
-  const bool regular = G.dev.w > 0 && offd >= 0.75 * G.dev.w;
-  G.dev.full = fe ? (fe[0] == '1') : (li == 0 || regular || G.dev.n <= (1u << 19));
-}
-
-// Host AMG setup (amg_setup.cpp): the assembled scalar matrix is downloaded,
-// the whole hierarchy is built on the host and every level image uploaded
-// (fallback of build_amg_device, or CFD_AMG_SETUP=host).
-void Solver::build_amg_host() {
-  const size_t ld = topo.ld;
-  std::vector<float> ell((size_t)topo.ws * ld);
-  CFD_HIP(hipMemcpyAsync(ell.data(), sval, ell.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-  sync();
-  std::vector<float> own(topo.scol.size());
-  for (uint32_t i = 0; i < N; ++i)
-    for (uint32_t k = topo.srow[i]; k < topo.srow[i + 1]; ++k) own[k] = ell[(size_t)(k - topo.srow[i]) * ld + i];
-  HostCsr A0;
-  std::vector<AmgHostLevel> H;
-  if (!dist()) {
-    A0.rows = A0.cols = N;
-    A0.row = topo.srow;
-    A0.col = topo.scol;
-    A0.val = std::move(own);
-    H = build_amg_hierarchy(A0, kMaxAmgLevels, {}, false, 0, cfg.log_level >= 2);
-  } else {
-    // all-gather the global pattern and the values (row order = global order, rank by rank)
-    const std::vector<uint64_t> nz = allgather_u64(topo.scol.size());
-    std::vector<uint64_t> eoff(R + 1, 0);
-    for (int q = 0; q < R; ++q) eoff[q + 1] = eoff[q] + nz[q];
-    std::vector<size_t> roff(R + 1), coff(R + 1);
-    for (int q = 0; q <= R; ++q) {
-      roff[q] = starts[q] * sizeof(uint32_t);
-      coff[q] = eoff[q] * sizeof(uint32_t);
-    }
-    const size_t nnz_all = eoff[R];
-    std::vector<uint32_t> lens(NG, 0);
-    for (uint32_t i = 0; i < N; ++i) lens[starts[rk] + i] = topo.srow[i + 1] - topo.srow[i];
-    uint32_t* d_lens = arena.alloc<uint32_t>(NG);
-    uint32_t* d_cols = arena.alloc<uint32_t>(nnz_all);
-    float* d_vals = arena.alloc<float>(nnz_all);
-    CFD_HIP(hipMemcpyAsync(d_lens, lens.data(), (size_t)NG * 4, hipMemcpyHostToDevice, stream));
-    CFD_HIP(hipMemcpyAsync(d_cols + eoff[rk], topo.scol.data(), topo.scol.size() * 4, hipMemcpyHostToDevice, stream));
-    CFD_HIP(hipMemcpyAsync(d_vals + eoff[rk], own.data(), own.size() * 4, hipMemcpyHostToDevice, stream));
-    comm->allgatherv_inplace(d_lens, roff, stream);
-    comm->allgatherv_inplace(d_cols, coff, stream);
-    comm->allgatherv_inplace(d_vals, coff, stream);
-    A0.rows = A0.cols = NG;
-    A0.row.assign((size_t)NG + 1, 0);
-    A0.col.resize(nnz_all);
-    A0.val.resize(nnz_all);
-    CFD_HIP(hipMemcpyAsync(lens.data(), d_lens, (size_t)NG * 4, hipMemcpyDeviceToHost, stream));
-    CFD_HIP(hipMemcpyAsync(A0.col.data(), d_cols, nnz_all * 4, hipMemcpyDeviceToHost, stream));
-    CFD_HIP(hipMemcpyAsync(A0.val.data(), d_vals, nnz_all * 4, hipMemcpyDeviceToHost, stream));
-    sync();
-    for (uint32_t i = 0; i < NG; ++i) A0.row[i + 1] = A0.row[i] + lens[i];
-    H = build_amg_hierarchy(A0, kMaxAmgLevels, starts, amg_local, amg_replicate_rows(), cfg.log_level >= 2 && rk == 0);
-  }
-  const int L = (int)H.size();
-  // distributed levels [0, amg_g): the rest are replicated (all of them on one GPU)
-  amg_g = 0;
-  if (dist()) {
-    const uint64_t rep = amg_replicate_rows();
-    amg_g = L;
-    for (int li = 1; li < L; ++li)
-      if (H[li].A.rows <= rep) {
-        amg_g = li;
-        break;
-      }
-  }
-  // Ghost lists of every rank on the distributed levels (the halo plans need
-  // both directions): the matrix columns outside the rank's rows, plus on a
-  // coarse level the aggregates of the rank's finer rows that another rank
-  // owns (an aggregate belongs to its seed's rank and may reach into the next
-  // ranks: the prolongation reads those coarse values, the restriction the
-  // fine residuals of members owned by the next ranks, which are matrix
-  // neighbours of the seed and so already ghosts of the seed's rank).
-  std::vector<std::vector<std::vector<uint32_t>>> ghosts(amg_g);
-  for (int li = 0; li < amg_g; ++li) {
-    const AmgHostLevel& HL = H[li];
-    ghosts[li].resize(R);
-#pragma omp parallel for schedule(dynamic, 1)
-    for (int q = 0; q < R; ++q) {
-      auto& gq = ghosts[li][q];
-      const uint64_t C0 = HL.part[q], C1 = HL.part[q + 1];
-      for (uint64_t i = C0; i < C1; ++i)
-        for (uint32_t k = HL.A.row[i]; k < HL.A.row[i + 1]; ++k) {
-          const uint32_t c = HL.A.col[k];
-          if (c < C0 || c >= C1) gq.push_back(c);
-        }
-      if (li > 0) {
-        const AmgHostLevel& HF = H[li - 1];
-        for (uint64_t i = HF.part[q]; i < HF.part[q + 1]; ++i) {
-          const uint32_t a = HF.agg[i];
-          if (a < C0 || a >= C1) gq.push_back(a);
-        }
-      }
-      std::sort(gq.begin(), gq.end());
-      gq.erase(std::unique(gq.begin(), gq.end()), gq.end());
-    }
-  }
-  // signed local index of global row c of distributed level li on this rank
-  auto rel_of = [&](int li, uint64_t c) -> int32_t {
-    const AmgGpuLevel& G = levels[li];
-    if (c >= G.C0 && c < G.C1) return (int32_t)(c - G.C0);
-    const auto& gh = ghosts[li][rk];
-    const auto it = std::lower_bound(gh.begin(), gh.end(), (uint32_t)c);
-    if (it == gh.end() || *it != c) throw std::logic_error("AMG: row is neither owned nor a ghost");
-    const uint32_t k = (uint32_t)(it - gh.begin());
-    return k < G.glo ? (int32_t)k - (int32_t)G.glo : (int32_t)(G.npad + (k - G.glo));
-  };
-  levels.assign(L, AmgGpuLevel{});
-  auto zeroed = [&](size_t cnt) {
-    float* p = arena.alloc<float>(cnt + 64);
-    CFD_HIP(hipMemsetAsync(p, 0, (cnt + 64) * sizeof(float), stream));
-    return p;
-  };
-  for (int li = 0; li < L; ++li) {  // layouts first: P of level li needs level li + 1's
-    const AmgHostLevel& HL = H[li];
-    AmgGpuLevel& G = levels[li];
-    G.nglob = HL.A.rows;
-    G.part = HL.part;
-    G.C0 = HL.part[rk];
-    G.C1 = HL.part[rk + 1];
-    if (li < amg_g) {
-      G.dist = true;
-      const auto& gh = ghosts[li][rk];
-      G.glo = (uint32_t)(std::lower_bound(gh.begin(), gh.end(), (uint32_t)G.C0) - gh.begin());
-      G.ghi = (uint32_t)gh.size() - G.glo;
-      G.npad = (uint32_t)(((G.C1 - G.C0) + 63) & ~(uint64_t)63);
-    }
-  }
-  for (int li = 0; li < L; ++li) {
-    const AmgHostLevel& HL = H[li];
-    AmgGpuLevel& G = levels[li];
-    if (G.dist) {  // distributed level: owned rows + ghosts
-      const uint32_t n = (uint32_t)(G.C1 - G.C0);
-      std::vector<uint32_t> lrow(n + 1);
-      for (uint32_t i = 0; i <= n; ++i) lrow[i] = HL.A.row[G.C0 + i] - HL.A.row[G.C0];
-      const uint32_t* lcol = HL.A.col.data() + HL.A.row[G.C0];
-      level_image(HL.A, G.C0, n, [&](uint32_t c) { return rel_of(li, c); }, G, arena, stream, amg_wide_limit);
-      G.plan = build_halo_plan_lists(HL.part, rk, ghosts[li], G.glo, G.npad);
-      interior_rows(HL.part, rk, lrow.data(), n, lcol, G.plan.lo_end, G.plan.hi_begin);
-      make_plan_buffers(G.plan, 1);
-      if (li == 0) {
-        if (G.glo != topo.glo || G.ghi != topo.ghi || G.npad != topo.npad)
-          throw std::logic_error("AMG level 0 ghosts differ from the cell ghosts");
-        G.xt = valloc<float>(1);
-        G.r = valloc<float>(1);
-      } else {
-        const uint32_t sh = (G.glo + 63) & ~63u;
-        const size_t cnt = (size_t)sh + G.npad + G.ghi;
-        G.x = zeroed(cnt) + sh;
-        G.xt = zeroed(cnt) + sh;
-        G.b = zeroed(cnt) + sh;
-        G.r = zeroed(cnt) + sh;
-      }
-    } else {  // replicated (or single-GPU) level, global numbering
-      const uint32_t n = (uint32_t)HL.A.rows;
-      level_image(HL.A, 0, n, [](uint32_t c) { return (int32_t)c; }, G, arena, stream, amg_wide_limit);
-      G.npad = G.dev.stride;
-      G.xt = zeroed(G.npad);
-      G.r = zeroed(G.npad);
-      if (li > 0) {
-        G.x = zeroed(G.npad);
-        G.b = zeroed(G.npad);
-      }
-    }
-    set_amg_full_policy(G, li);
-    // coarsening operators: P as an aggregate index per stored fine row
-    // (signed local coarse index into a distributed next level, global id into
-    // a replicated one), R = P^T rows of this rank's aggregates with local fine
-    // members (owned, or ghosts of the next ranks)
-    if (HL.has_op) {
-      const AmgHostLevel& HC = H[li + 1];
-      const bool next_dist = levels[li + 1].dist;
-      std::vector<uint32_t> agg(G.dev.stride, 0), r_row, r_col;
-      if (G.dist) {
-        for (uint64_t i = G.C0; i < G.C1; ++i)
-          agg[i - G.C0] = next_dist ? (uint32_t)rel_of(li + 1, HL.agg[i]) : HL.agg[i];
-        const uint64_t I0 = HC.part[rk], I1 = HC.part[rk + 1];
-        r_row.resize(I1 - I0 + 1);
-        for (uint64_t I = I0; I <= I1; ++I) r_row[I - I0] = HL.r_row[I] - HL.r_row[I0];
-        r_col.assign(HL.r_col.begin() + HL.r_row[I0], HL.r_col.begin() + HL.r_row[I1]);
-        for (auto& f : r_col) {
-          const int32_t lf = rel_of(li, f);
-          if (lf < 0) throw std::logic_error("AMG: aggregate member below its seed's rank");
-          f = (uint32_t)lf;
-        }
-        G.dev.nc = (uint32_t)(I1 - I0);
-        // members live on this or higher ranks, seeds on this or lower ones: the
-        // aggregates with ghost members come last, the fine rows of lower-rank
-        // aggregates first
-        const uint32_t nown = (uint32_t)(G.C1 - G.C0);
-        G.rc_hi = G.dev.nc;
-        for (uint32_t I = 0; I < G.dev.nc; ++I) {
-          bool ghost = false;
-          for (uint32_t k = r_row[I]; k < r_row[I + 1]; ++k) ghost |= r_col[k] >= nown;
-          if (ghost) {
-            G.rc_hi = I;
-            break;
-          }
-        }
-        G.pf_lo = 0;
-        if (next_dist) {
-          const uint32_t ncl = G.dev.nc;
-          for (uint32_t i = 0; i < nown; ++i)
-            if ((int32_t)agg[i] < 0 || agg[i] >= ncl) G.pf_lo = i + 1;
-          G.pf_lo = std::min((G.pf_lo + 3) & ~3u, nown);
-        }
-      } else {
-        std::copy(HL.agg.begin(), HL.agg.end(), agg.begin());
-        r_row = HL.r_row;
-        r_col = HL.r_col;
-        G.dev.nc = HL.nc;
-      }
-      G.dev.agg = arena.upload(agg, stream, kAggSlack);
-      G.dev.r_row = arena.upload(r_row, stream);
-      G.dev.r_col = arena.upload(r_col, stream);
-      {
-        std::vector<int32_t> m4;
-        build_r_m4(r_row, r_col, m4);
-        G.dev.r_m4 = reinterpret_cast<const int4*>(arena.upload(m4, stream));
-      }
-    }
-  }
 }
 
 // Drop the hierarchy (its device memory included); the next AMG solve builds
@@ -1692,43 +1358,6 @@ void Solver::debug_prepare_assemble(bool asmb) {
   prepare();
   if (asmb) assemble();
   sync();
-}
-
-uint64_t Solver::amg_level_digest(int li) {
-  if (li < 0 || li >= (int)levels.size()) throw std::invalid_argument("no such AMG level");
-  CFD_HIP(hipSetDevice(device));
-  const AmgLevelDev& d = levels[li].dev;
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p, size_t bytes) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t k = 0; k < bytes; ++k) h = (h ^ b[k]) * 1099511628211ull;
-  };
-  auto dev = [&](const void* src, size_t bytes) {
-    if (!src || !bytes) return;
-    std::vector<unsigned char> tmp(bytes);
-    CFD_HIP(hipMemcpyAsync(tmp.data(), src, bytes, hipMemcpyDeviceToHost, stream));
-    sync();
-    mix(tmp.data(), bytes);
-  };
-  const uint32_t hdr[6] = {d.n, d.stride, (uint32_t)d.w, (uint32_t)d.use16, d.nc, (uint32_t)levels[li].nnz};
-  mix(hdr, sizeof(hdr));
-  const size_t slots = (size_t)std::max(d.w, 1) * d.stride;
-  dev(d.val, slots * 4);
-  dev(d.col16, d.use16 ? slots * 2 : 0);
-  dev(d.col32, d.use16 ? 0 : slots * 4);
-  dev(d.len, d.stride);
-  dev(d.drank, d.stride);
-  dev(d.dv, (size_t)d.stride * 4);
-  dev(d.de, (size_t)d.stride * 4);
-  if (d.nc) {
-    dev(d.agg, (size_t)d.stride * 4);
-    std::vector<uint32_t> rr((size_t)d.nc + 1);
-    CFD_HIP(hipMemcpyAsync(rr.data(), d.r_row, rr.size() * 4, hipMemcpyDeviceToHost, stream));
-    sync();
-    mix(rr.data(), rr.size() * 4);
-    dev(d.r_col, (size_t)rr[d.nc] * 4);
-  }
-  return h;
 }
 
 size_t Solver::debug_len(int id) const {

@@ -70,6 +70,16 @@ class DeviceArena {
   size_t bytes_ = 0;
 };
 
+// temporary device buffer (setup scratch; the arena holds what the V-cycle keeps)
+template <class T>
+struct DevTmp {
+  T* p = nullptr;
+  explicit DevTmp(size_t n) { CFD_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T))); }
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+  ~DevTmp() { (void)hipFree(p); }
+};
+
 // roctx range (rocprofv3 --marker-trace shows steps, Picard iterations,
 // FGMRES solves and iterations, AMG setup / refresh, checkpoint I/O)
 struct Range {
@@ -95,14 +105,9 @@ struct Topology {
   uint32_t npad = 0;           // N rounded up to 64: first upper-ghost local index
   uint32_t glo = 0, ghi = 0;   // ghosts below c0 / at or above c1
   std::vector<uint32_t> ghost; // ghost global ids, ascending
+  RowWindow window() const { return RowWindow(c0, c1, ghost, glo); }
   // signed local index of a global cell id (owned or ghost)
-  int32_t rel(uint32_t g) const {
-    if (g >= c0 && g < c1) return (int32_t)(g - c0);
-    const auto it = std::lower_bound(ghost.begin(), ghost.end(), g);
-    if (it == ghost.end() || *it != g) throw std::logic_error("cell is neither owned nor a ghost");
-    const uint32_t k = (uint32_t)(it - ghost.begin());
-    return k < glo ? (int32_t)k - (int32_t)glo : (int32_t)(npad + (k - glo));
-  }
+  int32_t rel(uint32_t g) const { return window().rel(g); }
   int wf = 0;  // max faces per cell
   int ws = 0;  // max scalar row length (incl. diagonal)
   std::vector<float> vol;
@@ -247,8 +252,33 @@ uint32_t aggregate_greedy(size_t n, const uint32_t* row, const uint32_t* col, co
 void transpose_aggregates(const std::vector<uint32_t>& agg, uint32_t nagg, std::vector<uint32_t>& r_row,
                           std::vector<uint32_t>& r_col);
 
+// Overlap ranges of a row-partitioned level's transfer operators, from its
+// local R (r_row, r_col: members as local fine rows, ghosts >= nown) and P
+// (agg[i], i < nown: signed local coarse index when the next level is
+// row-partitioned too).  Members live on this or higher ranks, seeds on this or
+// lower ones: the aggregates with ghost members come last, the fine rows of
+// lower ranks' aggregates first.  rc_hi: the first aggregate with a ghost
+// member (nc: none); pf_lo: one past the last fine row of a foreign aggregate,
+// rounded up to 4 (at most nown; 0 when the next level is replicated).
+struct TransferBounds {
+  uint32_t rc_hi = 0, pf_lo = 0;
+};
+TransferBounds transfer_bounds(const std::vector<uint32_t>& r_row, const std::vector<uint32_t>& r_col,
+                               const std::vector<uint32_t>& agg, uint32_t nown, uint32_t nc, bool next_dist);
+
 struct AmgGpuLevel {
   AmgLevelDev dev{};
+  // the image arrays of dev as the device setup writes them (alloc_level_image,
+  // pack_level); the host setup uploads finished arrays and leaves these null
+  struct Image {
+    float* val = nullptr;
+    int16_t* col16 = nullptr;
+    int32_t* col32 = nullptr;
+    uint8_t* len = nullptr;
+    uint8_t* drank = nullptr;
+    float* dv = nullptr;
+    float* de = nullptr;
+  } img;
   float* x = nullptr;   // level solution (level 0: external p_sol); owned base
   float* xt = nullptr;  // ping-pong partner for the out-of-place smoother
   bool wide = false;    // rows wider than the u8 layout: 16-bit lengths, tail kernels only
@@ -648,7 +678,22 @@ struct Solver {
   bool build_amg_device_dist();
   bool device_levels(AmgSetupLevel& cur, int li0, const std::vector<uint64_t>& part0);
   std::vector<std::vector<uint32_t>> allgatherv_u32(const std::vector<uint32_t>& mine);  // collective
+  bool any_rank(bool mine);  // collective
   void set_amg_full_policy(AmgGpuLevel& G, int li);
+  // ---- the level layout in device memory, shared by the three setups (amg_levels.cpp)
+  float* zeroed(size_t cnt);  // cnt + 64 zeroed floats (the slack of the 16-byte vector reads)
+  void set_level_header(AmgGpuLevel& G, uint32_t n, uint32_t stride, const LevelShape& shape, uint64_t nnz);
+  void alloc_level_image(AmgGpuLevel& G);                      // after set_level_header
+  void pack_level(const SetupMatrix& src, AmgGpuLevel& G);     // k_amg_pack into the allocated image
+  void level_image(const HostCsr& A, const RowWindow* win, AmgGpuLevel& G);  // the same bytes, built on the host
+  void alloc_level_vectors(AmgGpuLevel& G, int li);            // x / xt / b / r
+  // P (agg: the level's n rows, padded here to its stride) and R in the V-cycle layout; sets dev.nc
+  void upload_transfer(AmgGpuLevel& G, const std::vector<uint32_t>& agg, const std::vector<uint32_t>& r_row,
+                       const std::vector<uint32_t>& r_col);
+  // Galerkin count pass over nagg coarse rows: rowptr = their scanned row
+  // pointers; false on a capacity overflow (collective: on any rank)
+  bool galerkin_count(const SetupMatrix& A, const uint32_t* gal_agg, const uint32_t* r_row, const uint32_t* r_col,
+                      uint32_t nagg, bool collective, std::vector<uint32_t>& rowptr);
   void precondition(int j, float* z);
   void iteration(int j, float* pin);  // one FGMRES iteration's launches (fixed order, no host reads)
   void run_iteration(int j, float* pin, int variant);  // eager or graph replay

@@ -97,12 +97,7 @@ void build_topology(const cfd_mesh_view& m, Topology& t, uint32_t c0, uint32_t c
                                 " neighbours (scalar row width " + std::to_string(ws) + " > " +
                                 std::to_string(kLgUsedMask) + ")");
   // ghosts: off-range neighbours, ascending global id
-  t.ghost.clear();
-  for (uint32_t c : t.scol)
-    if (c < c0 || c >= c1) t.ghost.push_back(c);
-  std::sort(t.ghost.begin(), t.ghost.end());
-  t.ghost.erase(std::unique(t.ghost.begin(), t.ghost.end()), t.ghost.end());
-  t.glo = (uint32_t)(std::lower_bound(t.ghost.begin(), t.ghost.end(), c0) - t.ghost.begin());
+  t.glo = level_ghosts(c0, c1, t.srow.data(), N, t.scol.data(), nullptr, 0, t.ghost);
   t.ghi = (uint32_t)t.ghost.size() - t.glo;
 
   // scalar-row ELL image (signed local columns) + diagonal rank (init/mesh.rs:201-212),

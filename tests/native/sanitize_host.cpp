@@ -129,14 +129,142 @@ void check_schedule(const std::vector<cfd2::VcLevel>& lv, int tail_first, bool l
   if (tail_first == L) check(sweeps[L - 1] == 10, "ten coarsest sweeps");
 }
 
+// The level layout rules (RowWindow, level_ghosts, level_shape,
+// transfer_bounds) on hierarchy H, rank by rank: its levels of more than rep
+// rows from level 0 on are row-partitioned, as in Solver::build_amg_host.
+// tops: the ranks' cell topologies (level 0's window).  Returns the number of
+// row-partitioned levels.
+int check_layout(const std::vector<cfd2::AmgHostLevel>& H, int R, uint64_t rep,
+                 const std::vector<cfd2::Topology>& tops) {
+  const int L = (int)H.size();
+  int g = L;
+  for (int l = 1; l < L; ++l)
+    if (H[l].A.rows <= rep) {
+      g = l;
+      break;
+    }
+  auto ghosts_of = [&](int l, int q, std::vector<uint32_t>& gh) {
+    const uint64_t C0 = H[l].part[q], C1 = H[l].part[q + 1];
+    const cfd2::AmgHostLevel* F = l > 0 ? &H[l - 1] : nullptr;
+    return cfd2::level_ghosts(C0, C1, H[l].A.row.data() + C0, (uint32_t)(C1 - C0), H[l].A.col.data(),
+                              F ? F->agg.data() + F->part[q] : nullptr, F ? F->part[q + 1] - F->part[q] : 0, gh);
+  };
+  auto direct_shape = [](const cfd2::HostCsr& A, uint64_t C0, uint32_t n, const cfd2::RowWindow* w) {
+    cfd2::LevelShape s;
+    for (uint32_t i = 0; i < n; ++i) {
+      int off = 0;
+      for (uint32_t k = A.row[C0 + i]; k < A.row[C0 + i + 1]; ++k) {
+        if (A.col[k] == C0 + i) continue;
+        ++off;
+        const int64_t d = (int64_t)(w ? w->rel(A.col[k]) : (int32_t)A.col[k]) - (int64_t)i;
+        if (d < -32768 || d > 32767) s.small_delta = false;
+      }
+      s.wmax = std::max(s.wmax, off);
+    }
+    return s;
+  };
+  for (int l = 0; l < L; ++l) {
+    const cfd2::HostCsr& A = H[l].A;
+    if (l >= g) {  // replicated: global numbering, no window
+      const cfd2::LevelShape s = cfd2::level_shape(A.row.data(), A.col.data(), (uint32_t)A.rows, 0, nullptr);
+      const cfd2::LevelShape d = direct_shape(A, 0, (uint32_t)A.rows, nullptr);
+      check(s.wmax == d.wmax && s.small_delta == d.small_delta, "level_shape of a replicated level");
+      continue;
+    }
+    for (int q = 0; q < R; ++q) {
+      const uint64_t C0 = H[l].part[q], C1 = H[l].part[q + 1];
+      const uint32_t n = (uint32_t)(C1 - C0);
+      // level_ghosts against a brute-force set
+      std::vector<uint32_t> gh;
+      const uint32_t glo = ghosts_of(l, q, gh);
+      std::vector<char> in(A.rows, 0);
+      for (uint64_t i = C0; i < C1; ++i)
+        for (uint32_t k = A.row[i]; k < A.row[i + 1]; ++k) in[A.col[k]] = 1;
+      if (l > 0)
+        for (uint64_t i = H[l - 1].part[q]; i < H[l - 1].part[q + 1]; ++i) in[H[l - 1].agg[i]] = 1;
+      std::vector<uint32_t> brute;
+      uint32_t below = 0;
+      for (uint64_t c = 0; c < A.rows; ++c)
+        if (in[c] && (c < C0 || c >= C1)) {
+          brute.push_back((uint32_t)c);
+          below += c < C0;
+        }
+      check(gh == brute && glo == below, "level_ghosts differs from the brute-force set");
+      // rel: monotone in the global id, onto [-glo, 0) u [0, n) u [npad, npad + ghi)
+      const cfd2::RowWindow w(C0, C1, gh, glo);
+      check(w.n() == n && w.ghi() == gh.size() - glo && w.npad % 64 == 0 && w.npad >= n && w.npad < n + 64, "window");
+      std::vector<uint32_t> ids(gh.begin(), gh.begin() + glo);
+      for (uint64_t c = C0; c < C1; ++c) ids.push_back((uint32_t)c);
+      ids.insert(ids.end(), gh.begin() + glo, gh.end());
+      int64_t prev = -(int64_t)glo - 1;
+      for (size_t t = 0; t < ids.size(); ++t) {
+        const int64_t r = w.rel(ids[t]);
+        check(r > prev, "rel not strictly increasing in the global id");
+        check((r >= -(int64_t)glo && r < (int64_t)n) || (r >= w.npad && r < (int64_t)w.npad + w.ghi()),
+              "rel outside the window's local ranges");
+        check((r < 0) == (t < glo) && (r >= (int64_t)w.npad) == (t >= glo + n), "rel range of a ghost / owned row");
+        if (l == 0) check(r == tops[q].rel(ids[t]), "rel differs from Topology::rel on level 0");
+        prev = r;
+      }  // strictly increasing, ids.size() values inside a union of ids.size() integers: a bijection
+      if (l == 0) check(gh == tops[q].ghost && glo == tops[q].glo && w.npad == tops[q].npad, "level 0 window");
+      uint64_t stranger = A.rows;  // past the level; else the first row that is neither owned nor a ghost
+      for (uint64_t c = 0; c < A.rows && stranger == A.rows; ++c)
+        if (!in[c] && (c < C0 || c >= C1)) stranger = c;
+      for (uint64_t c : {stranger, (uint64_t)A.rows}) {
+        bool threw = false;
+        try {
+          (void)w.rel(c);
+        } catch (const std::logic_error&) {
+          threw = true;
+        }
+        check(threw, "rel of a row that is neither owned nor a ghost must throw");
+      }
+      // level_shape against a direct scan
+      const cfd2::LevelShape s = cfd2::level_shape(A.row.data() + C0, A.col.data(), n, C0, &w);
+      const cfd2::LevelShape d = direct_shape(A, C0, n, &w);
+      check(s.wmax == d.wmax && s.small_delta == d.small_delta, "level_shape differs from a direct scan");
+      // transfer_bounds over this rank's local P and R
+      if (!H[l].has_op) continue;
+      const bool next_dist = l + 1 < g;
+      std::vector<uint32_t> ngh;
+      const uint32_t nglo = next_dist ? ghosts_of(l + 1, q, ngh) : 0;
+      const uint64_t I0 = H[l + 1].part[q], I1 = H[l + 1].part[q + 1];
+      const cfd2::RowWindow nw(I0, I1, ngh, nglo);
+      const uint32_t nc = (uint32_t)(I1 - I0);
+      std::vector<uint32_t> agg(w.npad, 0), r_row(nc + 1), r_col;
+      for (uint32_t i = 0; i < n; ++i) agg[i] = next_dist ? (uint32_t)nw.rel(H[l].agg[C0 + i]) : H[l].agg[C0 + i];
+      for (uint32_t I = 0; I <= nc; ++I) r_row[I] = H[l].r_row[I0 + I] - H[l].r_row[I0];
+      for (uint32_t k = H[l].r_row[I0]; k < H[l].r_row[I1]; ++k) {
+        const int32_t lf = w.rel(H[l].r_col[k]);
+        check(lf >= 0, "aggregate member below its seed's rank");
+        r_col.push_back((uint32_t)lf);
+      }
+      const cfd2::TransferBounds tb = cfd2::transfer_bounds(r_row, r_col, agg, n, nc, next_dist);
+      check(tb.rc_hi <= nc && tb.pf_lo <= n, "transfer bounds range");
+      for (uint32_t I = 0; I < nc; ++I) {
+        bool ghost = false;
+        for (uint32_t k = r_row[I]; k < r_row[I + 1]; ++k) ghost = ghost || r_col[k] >= n;
+        if (I < tb.rc_hi) check(!ghost, "an aggregate below rc_hi has a ghost member");
+        if (I == tb.rc_hi) check(ghost, "aggregate rc_hi has only owned members");
+      }
+      check(tb.pf_lo % 4 == 0 || tb.pf_lo == n, "pf_lo neither a multiple of 4 nor the row count");
+      if (!next_dist) check(tb.pf_lo == 0, "pf_lo into a replicated level");
+      for (uint32_t i = tb.pf_lo; i < n && next_dist; ++i)
+        check((int32_t)agg[i] >= 0 && agg[i] < nc, "a fine row at or above pf_lo belongs to a foreign aggregate");
+    }
+  }
+  return g;
+}
+
 void run(const char* name, const cfd2::Mesh& m) {
   const cfd_mesh_view v = view_of(m);
   const uint32_t n = m.num_cells();
   for (int R = 1; R <= 4 && (uint32_t)R <= cfd2::red_geom(n).nseg; ++R) {
     const auto starts = cfd2::partition_starts(n, R);
     uint64_t rows = 0, nnz = 0, sends = 0, recvs = 0, reg_rows = 0;
+    std::vector<cfd2::Topology> tops(R);
     for (int r = 0; r < R; ++r) {
-      cfd2::Topology t;
+      cfd2::Topology& t = tops[r];
       cfd2::build_topology(v, t, (uint32_t)starts[r], (uint32_t)starts[r + 1]);
       const cfd2::HaloPlan p =
           cfd2::build_halo_plan(starts, r, t.srow.data(), t.N, t.scol.data(), t.ghost, t.glo, t.npad);
@@ -197,6 +325,13 @@ void run(const char* name, const cfd2::Mesh& m) {
           for (uint64_t i = HL[l].part[q]; i < HL[l].part[q + 1]; ++i)
             check(HL[l].agg[i] >= HL[l + 1].part[q] && HL[l].agg[i] < HL[l + 1].part[q + 1],
                   "partition-aware aggregate straddles ranks");
+      check_layout(HL, R, 40, tops);
+    }
+    {  // the level layout rules, levels of more than 40 rows row-partitioned
+      const int g = check_layout(H, R, 40, tops);
+      check(g >= 2, "fewer than two row-partitioned levels");
+      std::printf("%s: %d rank(s): level layout rules on %d row-partitioned levels of %zu: ok\n", name, R, g,
+                  H.size());
     }
     for (size_t l = 0; l + 1 < H.size(); ++l)
       check(H[l].has_op && H[l + 1].A.rows == H[l].nc, "level sizes");

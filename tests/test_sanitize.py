@@ -31,8 +31,9 @@ def test_oracle_and_mesh_code_under_asan_ubsan(tmp_path):
                     reason="g++ / ROCm headers not available")
 def test_host_setup_code_under_asan_ubsan(tmp_path):
     """The product's GPU-free host setup code: slab topology and halo plans for
-    1-4 ranks, the host AMG hierarchy and the V-cycle schedules planned over it
-    (tests/native/sanitize_host.cpp)."""
+    1-4 ranks, the host AMG hierarchy, the level layout rules (row windows,
+    ghost lists, level shapes, transfer bounds) and the V-cycle schedules planned
+    over it (tests/native/sanitize_host.cpp)."""
     exe = str(tmp_path / "sanitize_host")
     srcs = [os.path.join(ROOT, p) for p in ("tests/native/sanitize_host.cpp", "cfd-demo2_amd/csrc/host/topology.cpp",
                                             "cfd-demo2_amd/csrc/host/amg_setup.cpp", "cfd-demo2_amd/csrc/host/dist.cpp",
@@ -49,6 +50,7 @@ def test_host_setup_code_under_asan_ubsan(tmp_path):
     # every mesh: 1 rank up to min(4, its reduction segments of 256 cells) ranks
     for mesh in ("cut-cell step", "voronoi channel", "delaunay channel"):
         assert all(f"{mesh}: " in r.stdout and f", {R} rank(s):" in r.stdout for R in (1, 2, 3)), r.stdout
-    # per mesh and rank count: the hierarchy line and the V-cycle schedule line
-    assert r.stdout.count(": ok") >= 18, r.stdout
-    assert r.stdout.count("V-cycle schedules over") * 2 == r.stdout.count(": ok"), r.stdout
+    # per mesh and rank count: the hierarchy line, the level layout line and the V-cycle schedule line
+    assert r.stdout.count(": ok") >= 27, r.stdout
+    assert r.stdout.count("V-cycle schedules over") * 3 == r.stdout.count(": ok"), r.stdout
+    assert r.stdout.count("level layout rules on") * 3 == r.stdout.count(": ok"), r.stdout
