@@ -152,6 +152,34 @@ class FlowDiag(C.Structure):  # cfd_flow_diag
                     force_viscous=tuple(self.force_viscous), region_faces=self.region_faces)
 
 
+class ScalarParams(C.Structure):  # cfd_scalar_params
+    _fields_ = [("diffusivity", C.c_float), ("inlet_value", C.c_float)]
+
+
+class ScalarConfig(C.Structure):  # cfd_scalar_config
+    _fields_ = [
+        ("tol", C.c_float),
+        ("max_sweeps", C.c_int32),
+        ("check_interval", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class ScalarStats(C.Structure):  # cfd_scalar_stats
+    _fields_ = [
+        ("sweeps", C.c_uint32),
+        ("converged", C.c_int32),
+        ("last_delta", C.c_float),
+        ("dt_used", C.c_float),
+        ("min", C.c_double),
+        ("max", C.c_double),
+        ("integral", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     _fields_ = [
         ("magic", C.c_char * 8),
@@ -217,6 +245,8 @@ EXPORTED = [
     "cfd_comm_timing_enable", "cfd_comm_timing",
     "cfd_flow_diagnostics", "cfd_get_derived", "cfd_set_force_region", "cfd_min_cell_size",
     "cfd_adaptive_dt_rule", "cfd_adapt_dt", "cfd_group_flow_diagnostics", "cfd_group_adapt_dt",
+    "cfd_scalar_config_default", "cfd_scalars_enable", "cfd_set_scalar_params", "cfd_set_scalar", "cfd_get_scalar",
+    "cfd_scalar_advance", "cfd_scalar_stats_get",
 ]
 
 _lib = None

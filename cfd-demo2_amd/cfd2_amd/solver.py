@@ -106,6 +106,14 @@ def _bind():
     L.cfd_adapt_dt.argtypes = [_vp, C.c_double, C.POINTER(C.c_float)]
     L.cfd_group_flow_diagnostics.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(_ffi.FlowDiag)]
     L.cfd_group_adapt_dt.argtypes = [C.POINTER(_vp), C.c_int32, C.c_double, C.POINTER(C.c_float)]
+    L.cfd_scalar_config_default.argtypes = [C.POINTER(_ffi.ScalarConfig)]
+    L.cfd_scalar_config_default.restype = None
+    L.cfd_scalars_enable.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarConfig)]
+    L.cfd_set_scalar_params.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarParams)]
+    L.cfd_set_scalar.argtypes = [_vp, C.c_int32, dp]
+    L.cfd_get_scalar.argtypes = [_vp, C.c_int32, dp]
+    L.cfd_scalar_advance.argtypes = [_vp, C.c_float]
+    L.cfd_scalar_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarStats)]
     _bound = True
     return L
 
@@ -320,6 +328,44 @@ class GpuSolver:
         self.step()
         return self.adapt_dt(target_cfl)
 
+    # -- passive scalars (dye, temperature) advected by the solved flow -----------
+    def enable_scalars(self, count, tol=None, max_sweeps=None, check_interval=None) -> None:
+        """cfd_scalars_enable: (re)allocate ``count`` (1..4) zero fields; 0 frees them.
+        Unset options keep cfd_scalar_config_default's values."""
+        cfg = scalar_config_default()
+        if tol is not None:
+            cfg.tol = float(tol)
+        if max_sweeps is not None:
+            cfg.max_sweeps = int(max_sweeps)
+        if check_interval is not None:
+            cfg.check_interval = int(check_interval)
+        self._call("cfd_scalars_enable", int(count), C.byref(cfg))
+
+    def set_scalar_params(self, field, diffusivity, inlet_value) -> None:
+        p = _ffi.ScalarParams(float(diffusivity), float(inlet_value))
+        self._call("cfd_set_scalar_params", int(field), C.byref(p))
+
+    def set_scalar(self, field, phi) -> None:
+        a = np.ascontiguousarray(np.asarray(phi, dtype=np.float64).reshape(-1))
+        if a.size != self.num_cells:
+            raise ValueError("set_scalar expects one value per cell")
+        self._call("cfd_set_scalar", int(field), a.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def get_scalar(self, field) -> np.ndarray:
+        a = np.zeros(self.num_cells)
+        self._call("cfd_get_scalar", int(field), a.ctypes.data_as(C.POINTER(C.c_double)))
+        return a
+
+    def advance_scalars(self, dt=None) -> None:
+        """cfd_scalar_advance: every enabled field one implicit step of ``dt``
+        (default: the dt the last step() used) on the fluxes that step left."""
+        self._call("cfd_scalar_advance", 0.0 if dt is None else float(dt))
+
+    def scalar_stats(self, field) -> _ffi.ScalarStats:
+        st = _ffi.ScalarStats()
+        self._call("cfd_scalar_stats_get", int(field), C.byref(st))
+        return st
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -459,6 +505,13 @@ class GpuSolver:
         return out
 
 
+def scalar_config_default() -> _ffi.ScalarConfig:
+    """cfd_scalar_config_default (no handle and no GPU needed)."""
+    cfg = _ffi.ScalarConfig()
+    _bind().cfd_scalar_config_default(C.byref(cfg))
+    return cfg
+
+
 def adaptive_dt_rule(current_dt, target_cfl, min_cell_size, max_vel):
     """cfd_adaptive_dt_rule, the reference's driver-loop rule (src/ui/app.rs:897-909)
     in f64; no handle and no GPU needed.  Returns (next_dt, changed)."""
@@ -507,7 +560,8 @@ class GpuGroup:
     def __getattr__(self, name):
         # setters / state writers apply to every rank
         if name.startswith("set_") or name in ("update_constants", "initialize_history",
-                                               "profile_enable", "profile_reset", "synchronize"):
+                                               "profile_enable", "profile_reset", "synchronize",
+                                               "enable_scalars"):  # refused by every rank: one GPU only
             def f(*a, **k):
                 for r in self.ranks:
                     getattr(r, name)(*a, **k)

@@ -518,4 +518,67 @@ uint32_t flow_diag_blocks(uint32_t N);
 // maxout[0..2] = bits of max s (f64), max |omega|, max |div| (f32 bits, zero-extended)
 void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s);
 
+// ---- scalar.hip ----
+// Passive scalar transport (include/cfd2_amd.h, the last section): implicit
+// Euler, bounded first-order upwind, driven by the face-slot mass fluxes flux_s
+// of the last k_prepare.  All f32, every sum left to right in face-slot order.
+// Per owned cell i and slot k (e = k*N + i):
+//   a_t    = vol_i * density / dt
+//   diff_k = (density * D) * area_e / dist_e_e           (this order)
+//   cin_k  = flux_s_e < 0 ? -flux_s_e : 0                (= max(-F, 0))
+//   c_k    = cin_k + diff_k   internal and inlet slots;  0 wall and outlet slots
+//   diag_i = a_t + c_0 + c_1 + ...
+//   b_i    = a_t * phi_old_i, then + c_k * inlet_value per inlet slot
+// coef is slot-major with row stride ld (N rounded up to 64): coef[k*ld + i].
+struct ScalarAssembleArgs {
+  uint32_t N;
+  uint32_t ld;
+  FaceSlots fs;
+  const float* vol;
+  const float* flux_s;   // [k*N + i]
+  const float* phi_old;  // [N]
+  float density, dt, diffusivity, inlet_value;
+  float* coef;           // [k*ld + i], k < nface_i written
+  float* diag;           // [N]
+  float* b;              // [N]
+};
+void launch_scalar_assemble(const ScalarAssembleArgs& a, hipStream_t s);
+// One Jacobi sweep: phi_out_i = (b_i + sum over internal slots k of c_k *
+// phi_in[other_k]) / diag_i, the sum starting from b_i, a true division.  The
+// columns are fs.other as it stands (stride N).
+struct ScalarSweepArgs {
+  uint32_t N;
+  uint32_t ld;
+  const int32_t* other;   // fs.other
+  const uint32_t* nface;  // fs.nface
+  const float* coef;
+  const float* diag;
+  const float* b;
+  const float* phi_in;
+  float* phi_out;
+  uint32_t* blockmax;     // [scalar_sweep_blocks(N)] scratch of the delta form
+};
+uint32_t scalar_sweep_blocks(uint32_t N);
+// delta != null: the sweep also leaves delta[0] = bits of max_i |phi_out_i -
+// phi_in_i| (non-negative f32 values order as unsigned integers; a NaN
+// difference counts as +inf, 0x7f800000, so it never reads as converged)
+void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s);
+// Read-only statistics of one field: unit partials partial[k] (k < np) of
+// sum (double)vol_i * (double)phi_i in the canonical tree (as k_flow_diag
+// writes its sums), and mm[0], mm[1] = min and max of phi as order-preserving
+// keys (scalar_key_value decodes them; NaN cells are ignored, no cell: NaN).
+struct ScalarStatsArgs {
+  uint32_t N;
+  const float* vol;
+  const float* phi;
+  uint32_t U;          // chunks per unit (RedGeom::U)
+  uint32_t np;         // unit partials
+  double* partial;     // [np]
+  uint32_t* blockmm;   // [2 * flow_diag_blocks(N)] scratch
+};
+void launch_scalar_stats(const ScalarStatsArgs& a, uint32_t* mm, hipStream_t s);
+// key of an f32 bit pattern: increasing in the value over every non-NaN float
+__host__ __device__ inline uint32_t scalar_value_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
+__host__ __device__ inline uint32_t scalar_key_value(uint32_t key) { return (key & 0x80000000u) ? key & 0x7FFFFFFFu : ~key; }
+
 }  // namespace cfd2

@@ -524,6 +524,52 @@ cfd_status cfd_group_adapt_dt(cfd_solver* const* h, int32_t n, double target_cfl
   return st;
 }
 
+// ------------------------------------------------------- passive scalars
+void cfd_scalar_config_default(cfd_scalar_config* c) {
+  if (!c) return;
+  c->tol = 1e-6f;
+  c->max_sweeps = 200;
+  c->check_interval = 4;
+  c->reserved = 0;
+}
+cfd_status cfd_scalars_enable(cfd_solver* s, int32_t count, const cfd_scalar_config* cfg) {
+  CHECK_S(s);
+  cfd_scalar_config c;
+  if (cfg)
+    c = *cfg;
+  else
+    cfd_scalar_config_default(&c);
+  return guard([&] { s->s->scalars_enable(count, c); });
+}
+cfd_status cfd_set_scalar_params(cfd_solver* s, int32_t field, const cfd_scalar_params* p) {
+  CHECK_S(s);
+  if (!p) return set_error(CFD_ERR_INVALID, "null scalar params");
+  return guard([&] {
+    s->s->scalar_check(field);
+    if (!(p->diffusivity >= 0.0f)) throw std::invalid_argument("scalar diffusivity must be >= 0");
+    s->s->sc_field[field].par = *p;
+  });
+}
+cfd_status cfd_set_scalar(cfd_solver* s, int32_t field, const double* phi) {
+  CHECK_S(s);
+  if (!phi) return set_error(CFD_ERR_INVALID, "null phi");
+  return guard([&] { s->s->set_scalar(field, phi); });
+}
+cfd_status cfd_get_scalar(cfd_solver* s, int32_t field, double* phi) {
+  CHECK_S(s);
+  if (!phi) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->get_scalar(field, phi); });
+}
+cfd_status cfd_scalar_advance(cfd_solver* s, float dt) {
+  CHECK_S(s);
+  return guard([&] { s->s->scalar_advance(dt); });
+}
+cfd_status cfd_scalar_stats_get(cfd_solver* s, int32_t field, cfd_scalar_stats* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->scalar_stats(field, out); });
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

@@ -1,0 +1,174 @@
+// Passive scalar transport (include/cfd2_amd.h, the last section; kernels.hpp
+// "scalar.hip"): per advance and field one face-slot assembly from flux_s as
+// the last k_prepare left it, then Jacobi sweeps in batches of check_interval,
+// the host reading the last sweep's delta after each batch.
+#include <cmath>
+#include <cstring>
+
+#include "solver_impl.hpp"
+
+namespace cfd2 {
+
+void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
+  if (count < 0 || count > 4) throw std::invalid_argument("scalar field count must be 0..4");
+  if (dist())
+    throw std::invalid_argument("passive scalars run on one GPU only: a distributed handle has no halo exchange per "
+                                "Jacobi sweep");
+  if (count > 0) {
+    if (!(c.tol >= 0.0f)) throw std::invalid_argument("scalar config: tol must be >= 0");
+    if (c.check_interval < 1) throw std::invalid_argument("scalar config: check_interval must be >= 1");
+    if (c.max_sweeps < 1) throw std::invalid_argument("scalar config: max_sweeps must be >= 1");
+  }
+  CFD_HIP(hipSetDevice(device));
+  sync();
+  sc_arena.release();
+  sc_count = 0;
+  sc_alt = sc_coef = sc_diag = sc_b = nullptr;
+  sc_blockmax = sc_res = nullptr;
+  sc_partial = nullptr;
+  for (ScalarField& f : sc_field) f = ScalarField{};
+  if (count == 0) return;
+  const size_t ld = topo.ld;
+  const size_t nbm = std::max<size_t>(scalar_sweep_blocks(N), 2 * (size_t)flow_diag_blocks(N));
+  auto field = [&] {
+    float* p = sc_arena.alloc<float>(ld);
+    CFD_HIP(hipMemsetAsync(p, 0, ld * sizeof(float), stream));
+    return p;
+  };
+  for (int f = 0; f < count; ++f) sc_field[f].phi = field();
+  sc_alt = field();
+  sc_coef = sc_arena.alloc<float>((size_t)topo.wf * ld);
+  sc_diag = sc_arena.alloc<float>(ld);
+  sc_b = sc_arena.alloc<float>(ld);
+  sc_blockmax = sc_arena.alloc<uint32_t>(nbm);
+  sc_res = sc_arena.alloc<uint32_t>(8);
+  sc_partial = sc_arena.alloc<double>(pstride);
+  sync();
+  sc_cfg = c;
+  sc_cfg.reserved = 0;
+  sc_count = count;
+}
+
+void Solver::scalar_check(int field) const {
+  if (sc_count == 0) throw std::invalid_argument("passive scalars are not enabled (cfd_scalars_enable)");
+  if (field < 0 || field >= sc_count)
+    throw std::invalid_argument("scalar field index " + std::to_string(field) + " outside [0, " +
+                                std::to_string(sc_count) + ")");
+}
+
+void Solver::set_scalar(int field, const double* phi) {
+  scalar_check(field);
+  CFD_HIP(hipSetDevice(device));
+  std::vector<float> h(N);
+  for (uint32_t i = 0; i < N; ++i) h[i] = (float)phi[i];
+  CFD_HIP(hipMemcpyAsync(sc_field[field].phi, h.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice, stream));
+  sync();
+}
+
+void Solver::get_scalar(int field, double* phi) {
+  scalar_check(field);
+  CFD_HIP(hipSetDevice(device));
+  std::vector<float> h(N);
+  CFD_HIP(hipMemcpyAsync(h.data(), sc_field[field].phi, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, stream));
+  sync();
+  for (uint32_t i = 0; i < N; ++i) phi[i] = h[i];
+}
+
+void Solver::scalar_advance(float dt) {
+  if (sc_count == 0) throw std::invalid_argument("passive scalars are not enabled (cfd_scalars_enable)");
+  if (!(dt > 0.0f)) {
+    if (!(last_step_dt > 0.0f))
+      throw std::invalid_argument("cfd_scalar_advance: dt <= 0 asks for the dt of the last cfd_step, and there was none");
+    dt = last_step_dt;
+  }
+  const Range range("scalar advance");
+  CFD_HIP(hipSetDevice(device));
+  const uint32_t ci = (uint32_t)sc_cfg.check_interval;
+  const uint32_t max_sweeps = ((uint32_t)sc_cfg.max_sweeps + ci - 1) / ci * ci;
+  for (int fi = 0; fi < sc_count; ++fi) {
+    ScalarField& f = sc_field[fi];
+    ScalarAssembleArgs A{};
+    A.N = N;
+    A.ld = topo.ld;
+    A.fs = fs;
+    A.vol = d_vol;
+    A.flux_s = flux_s;
+    A.phi_old = f.phi;
+    A.density = constants.density;
+    A.dt = dt;
+    A.diffusivity = f.par.diffusivity;
+    A.inlet_value = f.par.inlet_value;
+    A.coef = sc_coef;
+    A.diag = sc_diag;
+    A.b = sc_b;
+    launch_scalar_assemble(A, stream);
+    check_launch("scalar assemble");
+    ScalarSweepArgs W{};
+    W.N = N;
+    W.ld = topo.ld;
+    W.other = fs.other;
+    W.nface = fs.nface;
+    W.coef = sc_coef;
+    W.diag = sc_diag;
+    W.b = sc_b;
+    W.blockmax = sc_blockmax;
+    f.sweeps = 0;
+    f.converged = 0;
+    f.dt_used = dt;
+    uint32_t bits = 0;
+    while (f.sweeps < max_sweeps) {
+      for (uint32_t k = 0; k < ci; ++k) {  // phi^0 = phi_old; b holds a_t * phi_old, so its buffer is free to swap
+        W.phi_in = f.phi;
+        W.phi_out = sc_alt;
+        launch_scalar_sweep(W, k + 1 == ci ? sc_res : nullptr, stream);
+        std::swap(f.phi, sc_alt);
+      }
+      check_launch("scalar sweep");
+      CFD_HIP(hipMemcpyAsync(&bits, sc_res, sizeof(bits), hipMemcpyDeviceToHost, stream));
+      sync();
+      f.sweeps += ci;
+      std::memcpy(&f.last_delta, &bits, 4);
+      if (!std::isfinite(f.last_delta))
+        throw std::domain_error("scalar field " + std::to_string(fi) + " diverged: non-finite Jacobi update after " +
+                                std::to_string(f.sweeps) + " sweeps");
+      if (f.last_delta <= sc_cfg.tol) {
+        f.converged = 1;
+        break;
+      }
+    }
+  }
+}
+
+void Solver::scalar_stats(int field, cfd_scalar_stats* out) {
+  scalar_check(field);
+  CFD_HIP(hipSetDevice(device));
+  const ScalarField& f = sc_field[field];
+  ScalarStatsArgs a{};
+  a.N = N;
+  a.vol = d_vol;
+  a.phi = f.phi;
+  a.U = red.U;
+  a.np = pstride;
+  a.partial = sc_partial;
+  a.blockmm = sc_blockmax;
+  launch_scalar_stats(a, sc_res + 2, stream);
+  launch_evolution_final(combine_d(sc_partial, 1), reinterpret_cast<double*>(sc_res + 4), stream);
+  check_launch("scalar stats");
+  uint32_t h[8];
+  CFD_HIP(hipMemcpyAsync(h, sc_res, sizeof(h), hipMemcpyDeviceToHost, stream));
+  sync();
+  const uint32_t bmin = scalar_key_value(h[2]), bmax = scalar_key_value(h[3]);
+  float vmin, vmax;
+  std::memcpy(&vmin, &bmin, 4);
+  std::memcpy(&vmax, &bmax, 4);
+  std::memset(out, 0, sizeof(*out));
+  out->sweeps = f.sweeps;
+  out->converged = f.converged;
+  out->last_delta = f.last_delta;
+  out->dt_used = f.dt_used;
+  out->min = vmin;
+  out->max = vmax;
+  std::memcpy(&out->integral, h + 4, sizeof(double));
+}
+
+}  // namespace cfd2

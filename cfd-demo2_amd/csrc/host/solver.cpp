@@ -244,6 +244,7 @@ Solver::~Solver() {
   comm.reset();
   arena.release();
   amg_arena.release();
+  sc_arena.release();
   if (cstream) (void)hipStreamDestroy(cstream);
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -1257,6 +1258,7 @@ void Solver::step() {  // coupled_solver.rs:33-499
   }
   rotate();
   constants.component = 0;
+  last_step_dt = constants.dt;  // host only: cfd_scalar_advance(dt <= 0) advances by the step's dt
   const int fault_rank = debug_fault_after_prepare;  // test hook, one step only
   debug_fault_after_prepare = -1;
   if (dist()) halo_state(true);  // the rotated slot's ghosts (last written 3 steps ago)

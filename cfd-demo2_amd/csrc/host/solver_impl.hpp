@@ -655,6 +655,37 @@ struct Solver {
   void get_derived(int kind, double* out);
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
+  // ---- passive scalars (scalar.cpp; kernels.hpp "scalar.hip") ----
+  // Opt-in: nothing below is allocated before scalars_enable, and step()
+  // launches none of it; step() only records the dt it used (last_step_dt).
+  // One GPU only.  Every buffer lives in sc_arena, released by
+  // scalars_enable(0).
+  struct ScalarField {
+    float* phi = nullptr;  // [ld] the current iterate (swaps with sc_alt during an advance)
+    cfd_scalar_params par{};
+    uint32_t sweeps = 0;
+    int32_t converged = 0;
+    float last_delta = 0.0f;
+    float dt_used = 0.0f;
+  };
+  DeviceArena sc_arena;
+  int sc_count = 0;
+  cfd_scalar_config sc_cfg{};
+  ScalarField sc_field[4];
+  float* sc_alt = nullptr;         // [ld] ping-pong partner of the field being advanced
+  float* sc_coef = nullptr;        // [wf * ld] slot coefficients of the field being advanced
+  float* sc_diag = nullptr;        // [ld]
+  float* sc_b = nullptr;           // [ld]
+  uint32_t* sc_blockmax = nullptr; // per-block scratch of the sweep's delta and the stats' min / max
+  uint32_t* sc_res = nullptr;      // [0] delta bits, [2..3] min / max keys, [4..5] the integral (f64)
+  double* sc_partial = nullptr;    // [pstride] unit partials of the integral
+  float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
+  void scalars_enable(int count, const cfd_scalar_config& c);
+  void scalar_check(int field) const;  // throws std::invalid_argument: not enabled / bad index
+  void set_scalar(int field, const double* phi);
+  void get_scalar(int field, double* phi);
+  void scalar_advance(float dt);
+  void scalar_stats(int field, cfd_scalar_stats* out);
   double algorithmic_step_bytes() const;
   double layout_step_bytes() const;
   double smoother_bytes() const;

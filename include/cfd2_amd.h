@@ -529,6 +529,70 @@ cfd_status cfd_adapt_dt(cfd_solver* s, double target_cfl, float* new_dt);
 cfd_status cfd_group_flow_diagnostics(cfd_solver* const* handles, int32_t nranks, cfd_flow_diag* out /* [nranks] */);
 cfd_status cfd_group_adapt_dt(cfd_solver* const* handles, int32_t nranks, double target_cfl, float* new_dt);
 
+/* ------------------------------------------------------------------------ */
+/* Passive scalar transport: up to 4 fields phi_f (dye, temperature,
+ * concentration) on the solver's mesh, advected by the conservative mass
+ * fluxes the last cfd_step left on the device and diffused with D_f.  Opt-in:
+ * a handle that never calls cfd_scalars_enable allocates and launches nothing
+ * new, and cfd_step launches none of it in any case.  Nothing cfd_step reads
+ * is written; cfd_step only records, on the host, the dt it used.
+ * The flux is that of the last k_prepare launch: the last Picard iteration's
+ * of the last cfd_step, formed from the state before that iteration's update
+ * (cfd_debug_prepare_assemble also refreshes it, from the current state).
+ * Discretisation (all f32, every sum left to right in face-slot order; F_k the
+ * mass flux out of cell i through its slot k, A_k the face area, d_k the
+ * centre distance the momentum diffusion uses):
+ *   time      a_t = vol_i * density / dt -- implicit Euler whatever
+ *             constants.time_scheme says
+ *   slot      c_k = max(-F_k, 0) + (density * D_f) * A_k / d_k on internal and
+ *             inlet faces; 0 on walls (zero flux) and outlets (zero gradient;
+ *             their flux is >= 0 by construction)
+ *   system    (a_t + sum_k c_k) phi_i - sum_{internal k} c_k phi_other(k)
+ *             = a_t phi_old_i + sum_{inlet k} c_k inlet_value
+ *   solve     Jacobi from phi_old, in batches of check_interval sweeps, until
+ *             max_i |phi^{m+1}_i - phi^m_i| <= tol or max_sweeps; running out
+ *             of sweeps is not an error (converged = 0)
+ * This is the bounded upwind form (div(u phi) - phi div(u)): every iterate is
+ * a convex combination of phi_old_i, the neighbours and inlet_value, so a dye
+ * in [0, 1] stays there up to rounding; the price is a conservation defect of
+ * sum_i phi_i div_i dt (cfd_flow_diag.max_divergence bounds div_i).
+ * One GPU only: handles of cfd_solver_create_dist* and members of a group
+ * of more than one rank return CFD_ERR_INVALID from cfd_scalars_enable.
+ * Checkpoints: cfd_state_save / cfd_state_load neither store nor touch the
+ * scalar fields (the file format and its version are unchanged);
+ * cfd_get_scalar / cfd_set_scalar round-trip the f32 values exactly, so a
+ * caller can keep them next to the state file.                              */
+typedef struct cfd_scalar_params {
+  float diffusivity;   /* D_f >= 0 (kinematic; multiplied by density) */
+  float inlet_value;   /* phi at inlet faces */
+} cfd_scalar_params;
+typedef struct cfd_scalar_config {
+  float tol;               /* stop when max |phi^{m+1} - phi^m| <= tol; default 1e-6 */
+  int32_t max_sweeps;      /* default 200; rounded up to a multiple of check_interval */
+  int32_t check_interval;  /* default 4; >= 1 */
+  int32_t reserved;
+} cfd_scalar_config;
+typedef struct cfd_scalar_stats {
+  uint32_t sweeps;       /* of the last cfd_scalar_advance, this field */
+  int32_t converged;
+  float last_delta;
+  float dt_used;
+  double min, max;       /* f32 values widened (NaN cells ignored) */
+  double integral;       /* sum vol * phi, f64, canonical order */
+} cfd_scalar_stats;
+void cfd_scalar_config_default(cfd_scalar_config* cfg);
+/* (Re)allocates `count` fields, all zero, with params {0, 0}; count 0 frees
+ * everything (later scalar calls then return CFD_ERR_INVALID).             */
+cfd_status cfd_scalars_enable(cfd_solver* s, int32_t count /* 1..4; 0 frees */, const cfd_scalar_config* cfg /* null: defaults */);
+cfd_status cfd_set_scalar_params(cfd_solver* s, int32_t field, const cfd_scalar_params* p);
+cfd_status cfd_set_scalar(cfd_solver* s, int32_t field, const double* phi /* [N] */);
+cfd_status cfd_get_scalar(cfd_solver* s, int32_t field, double* phi /* [N] */);
+/* dt > 0: that step; dt <= 0: the dt the last cfd_step used (CFD_ERR_INVALID if none yet).
+ * Advances every enabled field.  A NaN or infinite update returns
+ * CFD_ERR_DIVERGED.                                                         */
+cfd_status cfd_scalar_advance(cfd_solver* s, float dt);
+cfd_status cfd_scalar_stats_get(cfd_solver* s, int32_t field, cfd_scalar_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

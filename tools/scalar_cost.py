@@ -1,0 +1,132 @@
+"""Cost of the passive-scalar advance, and its sweep kernel against the level-0
+AMG smoother of the same session.
+
+At each bench configuration (default c1 and c2), on one handle after 2 steps
+(AMG preconditioner, the level-0 smoother timed during the second):
+  (a) the median of 20 fenced advance_scalars() calls (cfd_synchronize on both
+      sides) for one field with the default config (tol 1e-6, batches of 4
+      sweeps, one host read per batch), and the sweeps each call took;
+  (b) the same with max_sweeps = check_interval = 64: 64 sweeps and one host
+      read per call, so time / 64 is the sweep kernel's own time (plus 1/64 of
+      the assembly and the read); its layout bytes / that time is the rate;
+  (c) the level-0 smoother's layout-true rate from cfd_profile_smoother /
+      cfd_smoother_layout_bytes -- the yardstick: both kernels are one Jacobi
+      sweep over a slot-major ELL with a gather.
+Writes profiles/r08/scalar_cost.json.
+
+    python tools/scalar_cost.py [--configs c1 c2] [--mesh-cache-dir DIR]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cfd-demo2_amd"))
+sys.path.insert(0, ROOT)
+
+H = {"c1": 0.001723, "c2": 5.449e-4}  # bench.py CONFIGS
+# a dye: at D = 1e-4 and dt = 1e-3 the diffusion number D dt / h^2 is 0.03 (C1) and 0.34 (C2), below the
+# cell CFL, so Jacobi converges in tens of sweeps; it needs about (1 + CFL + 4 D dt / h^2) ln(1 / tol) of them
+DIFFUSIVITY = 1e-4
+
+
+def sweep_layout_bytes(mesh) -> float:
+    """Layout bytes of one k_scalar_sweep, each element once: per used face slot
+    the column (fs.other) and the coefficient (4 B each); per cell nface, diag,
+    b and the phi written (4 B each); the phi gathers counted once (4 B per cell)."""
+    slots = float(mesh.arrays()["cell_face_offsets"][-1])
+    return 8.0 * slots + 16.0 * mesh.num_cells() + 4.0 * mesh.num_cells()
+
+
+def fenced(solver, fn, reps=20):
+    ts, sweeps = [], []
+    for _ in range(reps):
+        solver.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        solver.synchronize()
+        ts.append(time.perf_counter() - t0)
+        sweeps.append(int(solver.scalar_stats(0).sweeps))
+    return statistics.median(ts), min(ts), sweeps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", nargs="+", default=["c1", "c2"], choices=sorted(H))
+    ap.add_argument("--mesh-cache-dir", default=None, help="load / save <dir>/<config>.mesh (bench.py --mesh-cache files)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "scalar_cost.json"))
+    args = ap.parse_args()
+    import numpy as np
+    from cfd2_amd import GpuSolver, build_id, default_config
+    from cfd2_amd.mesh import Mesh, bench_channel
+
+    rows = []
+    for name in args.configs:
+        cache = os.path.join(args.mesh_cache_dir, name + ".mesh") if args.mesh_cache_dir else None
+        if cache and os.path.exists(cache):
+            mesh = Mesh.load(cache)
+        else:
+            mesh = bench_channel(H[name], 100)
+            if cache:
+                mesh.save(cache)
+        s = GpuSolver(mesh, config=default_config(fixed_outer=5, fixed_inner=30))
+        s.set_dt(1e-3)
+        s.set_viscosity(0.01)
+        s.set_density(1.0)
+        s.set_alpha_u(0.7)
+        s.set_alpha_p(0.3)
+        s.set_precond_type(1)
+        s.initialize_history()
+        s.profile_enable(True)
+        s.step()           # includes the AMG setup
+        s.profile_reset()  # the smoother's times of the second step only
+        s.step()
+        sm_ms, sm_n, _ = s.profile_smoother()
+        s.profile_enable(False)
+        sm_bytes = s.smoother_layout_bytes()
+        x = mesh.arrays()["cell_cx"]
+        dye = np.where(x < 0.5, 1.0, 0.0)
+
+        def start(**cfg):
+            s.enable_scalars(1, **cfg)
+            s.set_scalar_params(0, DIFFUSIVITY, 1.0)
+            s.set_scalar(0, dye)
+            s.advance_scalars()  # warm-up: the first launches load the code objects
+
+        start()
+        a_med, a_min, a_sweeps = fenced(s, s.advance_scalars)
+        st = s.scalar_stats(0)
+        start(max_sweeps=64, check_interval=64)
+        b_med, b_min, b_sweeps = fenced(s, s.advance_scalars)
+        assert set(b_sweeps) == {64}
+        nbytes = sweep_layout_bytes(mesh)
+        row = dict(config=name, cells=mesh.num_cells(), build=build_id(), dt=1e-3, diffusivity=DIFFUSIVITY,
+                   advance_ms=1e3 * a_med, advance_min_ms=1e3 * a_min, advance_sweeps=a_sweeps,
+                   advance_converged=int(st.converged), phi_min=st.min, phi_max=st.max,
+                   fixed64_ms=1e3 * b_med, fixed64_min_ms=1e3 * b_min, sweep_us=1e6 * b_med / 64,
+                   sweep_layout_bytes=nbytes, sweep_gbs=nbytes / (b_med / 64) / 1e9,
+                   smoother_launches=int(sm_n), smoother_us=1e3 * sm_ms / max(sm_n, 1),
+                   smoother_layout_bytes=sm_bytes, smoother_gbs=sm_bytes / (1e-3 * sm_ms / max(sm_n, 1)) / 1e9)
+        row["sweep_rate_over_smoother_rate"] = row["sweep_gbs"] / row["smoother_gbs"]
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        s.close()
+        del mesh
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(dict(what="median of 20 fenced advance_scalars() calls for one field, one handle, after 2 steps "
+                            "(tools/scalar_cost.py); advance_* = the default config (a whole host call: the assembly, "
+                            "batches of 4 sweeps, one 4-byte read and stream synchronisation per batch); fixed64_* = "
+                            "64 sweeps and one read per call; smoother_* = the level-0 AMG smoother timed by device "
+                            "events during the second step of the same session",
+                       rows=rows), fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
