@@ -71,6 +71,7 @@ def _bind():
     L.cfd_debug_prepare_assemble.argtypes = [_vp, C.c_int32]
     L.cfd_debug_reference_semantics.argtypes = [_vp, C.c_int32]
     L.cfd_debug_amg_info.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+    L.cfd_debug_column_widths.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     u8p = C.POINTER(C.c_uint8)
     u32p = C.POINTER(C.c_uint32)
     L.cfd_dist_unique_id.argtypes = [u8p]
@@ -443,6 +444,15 @@ class GpuSolver:
             dig.append(int(d.value))
         return int(path.value), dig
 
+    def column_widths(self):
+        """(coupled use16, [use16 of every built AMG level]): 1 = the row kernels
+        read 16-bit column deltas, 0 = 32-bit absolute columns
+        (cfd_debug_column_widths; host fields only, nothing is launched)."""
+        cu, nl = C.c_int32(), C.c_int32()
+        lv = (C.c_int32 * 20)()
+        self._call("cfd_debug_column_widths", C.byref(cu), C.byref(nl), lv)
+        return int(cu.value), [int(lv[i]) for i in range(min(nl.value, 20))]
+
     def step_algorithmic_bytes(self) -> float:
         return float(_ffi.lib().cfd_step_algorithmic_bytes(self._h))
 
@@ -651,6 +661,11 @@ class GpuGroup:
 
     def step_info(self): return self.ranks[0].step_info()
     def amg_levels(self): return self.ranks[0].amg_levels()
+
+    def column_widths(self):
+        w = [r.column_widths() for r in self.ranks]
+        assert all(x == w[0] for x in w), f"ranks disagree on the column widths: {w}"
+        return w[0]
 
     @property
     def should_stop(self): return self.ranks[0].should_stop

@@ -283,6 +283,15 @@ cfd_status cfd_debug_amg_info(cfd_solver* s, int32_t level, int32_t* setup_path,
     if (digest) *digest = s->s->amg_level_digest(level);
   });
 }
+cfd_status cfd_debug_column_widths(const cfd_solver* s, int32_t* coupled_use16, int32_t* num_levels,
+                                   int32_t* level_use16) {
+  CHECK_S(s);
+  const auto& L = s->s->levels;
+  if (coupled_use16) *coupled_use16 = s->s->topo.use16 ? 1 : 0;
+  if (num_levels) *num_levels = (int32_t)L.size();
+  for (size_t i = 0; level_use16 && i < L.size() && i < 20; ++i) level_use16[i] = L[i].dev.use16;
+  return CFD_OK;
+}
 double cfd_smoother_layout_bytes(const cfd_solver* s) { return (s && s->s) ? s->s->smoother_layout_bytes() : 0.0; }
 double cfd_step_layout_bytes(const cfd_solver* s) { return (s && s->s) ? s->s->layout_step_bytes() : 0.0; }
 double cfd_step_algorithmic_bytes(const cfd_solver* s) {

@@ -317,6 +317,13 @@ cfd_status cfd_amg_levels(const cfd_solver* s, int32_t* num_levels, uint32_t* ro
  * (matrix, diagonal, P, R) -- host and device setups must agree bit-for-bit.
  * Debug/parity only; not part of the reference surface.                     */
 cfd_status cfd_debug_amg_info(cfd_solver* s, int32_t level, int32_t* setup_path, uint64_t* digest);
+/* Which column form the row kernels of this handle read: 1 = 16-bit deltas
+ * (col - row), 0 = 32-bit absolute columns.  coupled_use16: the coupled
+ * matrix and every kernel over the mesh topology; level_use16[i]: AMG level i
+ * (num_levels of them, 0 before the hierarchy is built).  Reads host fields
+ * only: allocates nothing, launches nothing.  Debug/parity only.            */
+cfd_status cfd_debug_column_widths(const cfd_solver* s, int32_t* coupled_use16, int32_t* num_levels,
+                                   int32_t* level_use16 /*[20]*/);
 /* Layout-true bytes of one level-0 smoother sweep: the minimum the kernel
  * moves in this library's level image (u8 lengths, ELL values + 16/32-bit
  * columns, b, x, diagonal, x_out); the roofline of record divides this by

@@ -1,5 +1,6 @@
 """Hand-built meshes for edge cases (a Mesh-like object over numpy arrays):
-single cell, a 1-D strip of cells, and deliberately broken meshes."""
+single cell, a 1-D strip of cells, deliberately broken meshes, and any mesh
+with its cells renumbered (renumbered() and the seeded permutation builders)."""
 import ctypes as C
 
 import numpy as np
@@ -139,6 +140,88 @@ def broken(kind):
         for k in a:
             a[k] = a[k][:0] if k != "cell_face_offsets" else np.zeros(1, np.uint32)
     return ArrayMesh(**a)
+
+
+CELL_ARRAYS = ("cell_cx", "cell_cy", "cell_vol")
+
+
+def renumbered(mesh, perm):
+    """The same mesh with its cells relabelled: perm[old] = new.  Faces keep
+    their numbers, arrays, owner / neighbour roles (so the normals stand) and
+    each cell keeps its own face order; only the cell ids in face_owner /
+    face_neighbor, the order of the per-cell arrays and the order of the
+    cell_faces runs change."""
+    a = mesh.arrays()
+    perm = np.asarray(perm, dtype=np.int64)
+    n = len(a["cell_cx"])
+    assert perm.shape == (n,) and np.array_equal(np.sort(perm), np.arange(n)), "perm is not a permutation"
+    old_of = np.empty(n, dtype=np.int64)  # old_of[new] = old
+    old_of[perm] = np.arange(n)
+    out = {k: np.array(v, copy=True) for k, v in a.items()}
+    own = a["face_owner"].astype(np.int64)
+    nb = a["face_neighbor"].astype(np.int64)
+    out["face_owner"] = perm[own].astype(np.uint32)
+    inner = nb != NONE
+    nb2 = np.full(len(nb), NONE, dtype=np.int64)
+    nb2[inner] = perm[nb[inner]]
+    out["face_neighbor"] = nb2.astype(np.uint32)
+    for k in CELL_ARRAYS:
+        out[k] = a[k][old_of]
+    offs = a["cell_face_offsets"].astype(np.int64)
+    cnt = (offs[1:] - offs[:-1])[old_of]
+    new_offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(cnt, out=new_offs[1:])
+    # slot s of new cell i reads old slot offs[old_of[i]] + (s - new_offs[i])
+    src = np.repeat(offs[:-1][old_of] - new_offs[:-1], cnt) + np.arange(int(new_offs[-1]))
+    out["cell_face_offsets"] = new_offs.astype(np.uint32)
+    out["cell_faces"] = a["cell_faces"][src]
+    return ArrayMesh(**out)
+
+
+def inverse_perm(perm):
+    perm = np.asarray(perm, dtype=np.int64)
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    return inv
+
+
+def perm_far_swap(n, k=64):
+    """First k cells exchanged with the last k: nearly every row keeps its
+    neighbours at the same small distances, a handful reach across the mesh."""
+    assert n >= 2 * k
+    perm = np.arange(n, dtype=np.int64)
+    perm[:k] = np.arange(n - k, n)
+    perm[n - k:] = np.arange(k)
+    return perm
+
+
+def perm_block_shuffle(n, block=1024, seed=2024):
+    """Blocks of `block` consecutive cells (the last one shorter) laid out in
+    seeded random order; the order inside a block stands."""
+    nb = -(-n // block)
+    order = np.random.default_rng(seed).permutation(nb)  # order[k] = old block placed k-th
+    size = np.minimum(block, n - order * block)
+    start = np.zeros(nb, dtype=np.int64)
+    np.cumsum(size[:-1], out=start[1:])
+    perm = np.empty(n, dtype=np.int64)
+    for k, ob in enumerate(order):
+        perm[ob * block:ob * block + size[k]] = start[k] + np.arange(size[k])
+    return perm
+
+
+def perm_random(n, seed=2024):
+    """A seeded permutation of all cells."""
+    return np.random.default_rng(seed).permutation(n).astype(np.int64)
+
+
+def red_units(n):
+    """(g, G, U) of the canonical reduction tree for n cells (kernels.hpp
+    red_geom): segments of G = 2^g chunks of 256 cells, written by the chunk
+    kernels as units of U = min(G, 4) chunks."""
+    g = 0
+    while g < 8 and (n >> (g + 1)) >= 16384:
+        g += 1
+    return g, 1 << g, min(1 << g, 4)
 
 
 def max_ranks(n):

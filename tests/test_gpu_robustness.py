@@ -85,7 +85,8 @@ def test_aligned_slot_ell_bitexact():
     """Coupled-matrix ELL with aligned slots (gaps where a wall removes a
     neighbour; Topology::tslot) on a quad mesh: the oracle's bits (amg_test
     setup, Jacobi and AMG preconditioners).  The positional layout of wider
-    meshes (ws > 8) is the Voronoi meshes' own (tests/test_voronoi.py)."""
+    meshes (ws > 8) is the Voronoi meshes' own (tests/test_voronoi.py); the
+    32-bit column forms of either layout: tests/test_gpu_wide_columns.py."""
     mesh = backwards_step()
     for precond in (0, 1):
         g = GpuSolver(mesh, config=default_config())
