@@ -1,8 +1,8 @@
 // The AMG V-cycle of the HIP solver (linear_solver/amg.rs:666-770): what the
 // setup decides after the hierarchy is built (fused forms, tail, pair images,
-// the launch schedule), the cycle that runs the schedule, the plain
-// dispatch-by-dispatch cycle of the reference-semantics mode, and the bytes
-// the schedule moves.  The schedule itself is plan_v_cycle (amg_setup.cpp).
+// the launch schedule), the cycle that runs the schedule, and the plain
+// dispatch-by-dispatch cycle of the reference-semantics mode.  The schedule
+// itself is plan_v_cycle (amg_setup.cpp); accounting.cpp prices it.
 #include <algorithm>
 #include <cstring>
 
@@ -593,70 +593,6 @@ void Solver::v_cycle_reference() {
     smooth(i);
   }
   if (levels[0].x != p_sol) throw std::logic_error("AMG level-0 ping-pong parity (reference semantics)");
-}
-
-// algorithmic bytes of one level-ℓ smoother sweep in the
-// reference CSR/f32/u32 format: 4(n+1) + 8 nnz + 12 n.
-double Solver::smoother_bytes() const {
-  if (levels.empty()) return 0.0;
-  const double n = levels[0].dev.n, nnz = (double)levels[0].nnz;
-  return 4.0 * (n + 1.0) + 8.0 * nnz + 12.0 * n;
-}
-
-// Layout-true bytes of one level-0 sweep of k_amg_smooth: what the kernel
-// must move in the AmgLevelDev image -- the u8 row lengths, every ELL slot's
-// value and column (16-bit delta or i32) over the padded rows, b, x, the
-// smoother diagonal and x_out (4 B each per row; the x gathers at the
-// neighbours counted once, as SURVEY §8(d) counts them).  At C2 (w = 4,
-// 16-bit deltas) 41 B per row against the reference format's 56.
-double Solver::smoother_layout_bytes() const {
-  if (levels.empty()) return 0.0;
-  const AmgLevelDev& d = levels[0].dev;
-  const double st = d.stride, n = d.n;
-  return st + std::max(d.w, 1) * st * (4.0 + (d.use16 ? 2.0 : 4.0)) + 16.0 * n;
-}
-
-// Layout-true bytes of one V-cycle over the level images: the sum over the
-// schedule's ops of what each launch moves (Solver::layout_step_bytes).
-// Known undercount, kept: the all-gather, the plain tail and the ten coarsest
-// sweeps count nothing.
-double Solver::v_cycle_layout_bytes() const {
-  auto row_image = [](const AmgLevelDev& d) {  // ELL values + columns over the padded rows
-    return std::max(d.w, 1) * (double)d.stride * (4.0 + (d.use16 ? 2.0 : 4.0));
-  };
-  auto n_of = [&](int i) { return (double)levels[i].dev.n; };
-  auto smooth = [&](int i) { return levels[i].dev.stride + row_image(levels[i].dev) + 16 * n_of(i); };
-  auto fused_rr = [&](int i) {  // fused residual + restriction
-    const double n = n_of(i), nc = n_of(i + 1), st = levels[i].dev.stride;
-    return 4 * nc + 4 * n + 2 * st + row_image(levels[i].dev) + 14 * n + 12 * nc;
-  };
-  // post-smoother reading x + P xc
-  auto smooth_prolong = [&](int i) { return smooth(i) + 4 * n_of(i) + 4 * n_of(i + 1); };
-  double vc = 0.0;
-  for (const VcOp& op : vc_plan) {
-    const int i = op.level;
-    const double n = n_of(i), st = levels[i].dev.stride;
-    switch (op.kind) {
-      // pre-smoother (coarse: zero-x, elementwise; not launched when fused into
-      // the previous level's restriction, whose 12 nc term counts it)
-      case VcKind::PreSmooth: vc += op.flag ? 12 * n : smooth(i); break;
-      case VcKind::ResRestrictFused: vc += fused_rr(i); break;
-      case VcKind::ResidualRestrict:  // residual, restriction
-        vc += (2 * st + row_image(levels[i].dev) + 16 * n) + (16 * n_of(i + 1) + 4 * n + 12 * n_of(i + 1));
-        break;
-      // k_amg_resrestrict_pair: its second level's b and x stay in LDS
-      case VcKind::ResRestrictPair: vc += fused_rr(i) + fused_rr(i + 1) - 8 * n_of(i + 1); break;
-      // single-workgroup tail (LDS image in)
-      case VcKind::TailBlob: vc += 4.0 * tail_blob_words + 16.0 * tail_vec_floats; break;
-      case VcKind::TakePreSmoothed: case VcKind::GatherRhs: case VcKind::Tail: case VcKind::CoarsestSweeps: break;
-      case VcKind::Prolong: vc += 12 * n + 4 * n_of(i + 1); break;
-      case VcKind::PostSmooth: vc += smooth(i); break;
-      case VcKind::PostSmoothProlong: vc += smooth_prolong(i); break;
-      // k_amg_prolong_smooth_pair: its coarse level's smoothed x stays in LDS
-      case VcKind::ProlongSmoothPair: vc += smooth_prolong(i) + smooth_prolong(i - 1) - 8 * n; break;
-    }
-  }
-  return vc;
 }
 
 }  // namespace cfd2

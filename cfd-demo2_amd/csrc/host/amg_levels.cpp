@@ -6,8 +6,11 @@
 // transfer_bounds (amg_setup.cpp); the Solver members here turn them into
 // device memory.  A builder decides only where a level's pattern and values
 // come from, how the aggregation runs and how the coarse rows are filled.
+// Also the hierarchy's lifetime: ensure_amg, drop_amg.
+#include <chrono>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "solver_impl.hpp"
 
@@ -194,6 +197,96 @@ void Solver::set_amg_full_policy(AmgGpuLevel& G, int li) {
   const double offd = ((double)G.nnz - n) / n;  // mean off-diagonals per row
   const bool regular = G.dev.w > 0 && offd >= 0.75 * G.dev.w;
   G.dev.full = fe ? (fe[0] == '1') : (li == 0 || regular || G.dev.n <= (1u << 19));
+}
+
+// Drop the hierarchy (its device memory included); the next AMG solve builds
+// a new one from the matrix of that moment (or from a loaded source).
+void Solver::drop_amg() {
+  CFD_HIP(hipSetDevice(device));
+  sync();
+  drop_graphs();  // they hold the hierarchy's pointers
+  levels.clear();
+  d_tail = nullptr;
+  tail_blob_first = -1;
+  d_tail_blob = nullptr;
+  d_tail_desc = nullptr;
+  tail_blob_words = tail_vec_floats = 0;
+  amg_refresh.clear();
+  rr_pair.clear();  // their block images lived in amg_arena
+  up_pair.clear();
+  vc_plan.clear();
+  amg_setup_flag = nullptr;
+  amg_refresh_pending = false;
+  amg_arena.release();
+  amg_built = false;
+  amg_setup_path = 0;
+  amg_age = 0;
+}
+
+void Solver::ensure_amg() {
+  if (amg_built) {
+    if (amg_refresh_pending) {
+      const Range range("amg refresh");
+      refresh_amg();
+      amg_refresh_pending = false;
+      amg_age = 0;
+    }
+    return;
+  }
+  const Range range("amg setup");
+  const bool timing = cfg.log_level >= 2 && rk == 0;
+  const auto t_start = std::chrono::steady_clock::now();
+  const char* se = knob(Knob::AmgSetup);
+  if (se && std::strcmp(se, "host") && std::strcmp(se, "device") && std::strcmp(se, "rebuild"))
+    throw std::invalid_argument(std::string("CFD_AMG_SETUP: expected device, host or rebuild, got ") + se);
+  const bool device_setup = !(se && std::string(se) == "host");
+  const char* how = "device";
+  amg_setup_path = 2;
+  const size_t slots_s = (size_t)topo.ws * topo.ld;
+  if (!amg_src) amg_src = arena.alloc<float>(slots_s);
+  const bool from_checkpoint = amg_src_loaded;  // then amg_age is the saved run's
+  if (!from_checkpoint)  // keep the source matrix for cfd_state_save
+    CFD_HIP(hipMemcpyAsync(amg_src, sval, slots_s * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  amg_src_loaded = false;
+  // both setup paths read `sval`: point it at the source for the build; the
+  // hierarchy's allocations go to amg_arena (arena swapped for the build)
+  float* const live = sval;
+  sval = amg_src;
+  amg_arena.release();
+  arena.swap(amg_arena);
+  struct Restore {
+    Solver* s;
+    float* live;
+    ~Restore() {
+      s->sval = live;
+      s->arena.swap(s->amg_arena);
+    }
+  } restore{this, live};
+  if (!(device_setup && build_amg_device())) {
+    how = "host";
+    amg_setup_path = 1;
+    levels.clear();
+    arena.release();  // the device attempt's partial hierarchy
+    build_amg_host();
+  }
+  finish_amg_schedule();
+  sync();
+  amg_built = true;
+  if (!from_checkpoint) amg_age = 0;
+  if (timing) {
+    std::string pairs, ups;  // the pairs the schedule runs, either leg by ascending level
+    for (const VcOp& op : vc_plan) {
+      const std::string a = " " + std::to_string(op.level) + "+";
+      if (op.kind == VcKind::ResRestrictPair) pairs += a + std::to_string(op.level + 1);
+      if (op.kind == VcKind::ProlongSmoothPair) ups = a + std::to_string(op.level - 1) + ups;
+    }
+    std::fprintf(stderr,
+                 "[amg setup] %s path: %d levels in %.3f s, tail from level %d (LDS image from level %d), "
+                 "down-leg pairs:%s, up-leg pairs:%s\n",
+                 how, (int)levels.size(),
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), tail_first,
+                 tail_blob_first, pairs.empty() ? " none" : pairs.c_str(), ups.empty() ? " none" : ups.c_str());
+  }
 }
 
 // Host AMG setup (fallback of build_amg_device, or CFD_AMG_SETUP=host;

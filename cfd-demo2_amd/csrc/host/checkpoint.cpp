@@ -48,11 +48,9 @@ constexpr uint64_t kCellFloats = 6;  // u(2) p d_p grad_p(2) per cell per FluidS
 struct Layout {
   uint64_t ng, nnz;
   uint64_t state(int slot) const { return 512 + (uint64_t)slot * kCellFloats * 4 * ng; }  // slot 3 = prev
-  // within a FluidState block: u[2N], p[N], d_p[N], grad_p[2N]
-  static uint64_t u_off(uint64_t) { return 0; }
-  static uint64_t p_off(uint64_t n) { return 8 * n; }
-  static uint64_t dp_off(uint64_t n) { return 12 * n; }
-  static uint64_t gp_off(uint64_t n) { return 16 * n; }
+  // within a FluidState block: u[2N], p[N], d_p[N], grad_p[2N], back to back
+  // in for_each_field's order
+  uint64_t field_bytes(int comps) const { return 4 * (uint64_t)comps * ng; }
   uint64_t x() const { return state(4); }
   uint64_t rowptr() const { return x() + 12 * ng; }
   uint64_t val() const { return rowptr() + (nnz ? 8 * (ng + 1) : 0); }
@@ -81,7 +79,7 @@ void Solver::save_state(const char* path) {
   sync();
   // a lagged residual read still pending is part of the state: complete it
   // now (the value is the one the next read would take)
-  flush_inner();
+  inner.flush();
   // collective: every rank learns the AMG source size and its value offset
   // a pending refresh stands for a dropped hierarchy (the next AMG solve re-makes it)
   const bool have_amg = (amg_built && !amg_refresh_pending) || amg_src_loaded;
@@ -112,8 +110,8 @@ void Solver::save_state(const char* path) {
         h.amg_nnz = nnz;
         h.step_index = step_index;
         h.have_prev = have_prev ? 1 : 0;
-        h.inner_has_last = inner.has_last ? 1 : 0;
-        h.inner_last = inner.last;
+        h.inner_has_last = inner.have() ? 1 : 0;
+        h.inner_last = inner.last();
         h.n_variance = (uint32_t)variance_history.size();
         for (size_t k = 0; k < variance_history.size(); ++k) {
           h.variance[k][0] = variance_history[k].first;
@@ -128,7 +126,7 @@ void Solver::save_state(const char* path) {
       }
       // owned rows of every per-cell array at their global offsets
       std::vector<float> buf(3 * (size_t)N);
-      auto put = [&](const void* dev, int comps, uint64_t sec) {
+      auto put = [&](const float* dev, int comps, uint64_t sec) {
         const size_t bytes = (size_t)N * comps * sizeof(float);
         CFD_HIP(hipMemcpyAsync(buf.data(), dev, bytes, hipMemcpyDeviceToHost, stream));
         sync();
@@ -136,11 +134,11 @@ void Solver::save_state(const char* path) {
       };
       for (int s = 0; s < 4; ++s) {
         const StateView& v = s < 3 ? ring[s] : prev;
-        const uint64_t b = L.state(s);
-        put(v.u, 2, b + Layout::u_off(NG));
-        put(v.p, 1, b + Layout::p_off(NG));
-        put(v.dp, 1, b + Layout::dp_off(NG));
-        put(v.gp, 2, b + Layout::gp_off(NG));
+        uint64_t sec = L.state(s);
+        for_each_field(v, [&](float* dev, int comps) {
+          put(dev, comps, sec);
+          sec += L.field_bytes(comps);
+        });
       }
       put(x, 3, L.x());
       if (nnz) {
@@ -222,29 +220,27 @@ void Solver::load_state(const char* path) {
     }
   }
   std::vector<float> img;
-  auto put = [&](void* dev, int comps, uint64_t sec) {  // owned + ghosts
+  auto put = [&](float* dev, int comps, uint64_t sec) {  // owned + ghosts
     local_image(reinterpret_cast<const float*>(base + sec), comps, img);
-    CFD_HIP(hipMemcpyAsync(static_cast<float*>(dev) - (size_t)shift * comps, img.data(), img.size() * sizeof(float),
-                           hipMemcpyHostToDevice, stream));
+    CFD_HIP(hipMemcpyAsync(dev - (size_t)shift * comps, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice,
+                           stream));
     sync();
   };
   for (int s = 0; s < 3; ++s) {
-    const uint64_t b = L.state(s);
-    put(ring[s].u, 2, b + Layout::u_off(NG));
-    put(ring[s].p, 1, b + Layout::p_off(NG));
-    put(ring[s].dp, 1, b + Layout::dp_off(NG));
-    put(ring[s].gp, 2, b + Layout::gp_off(NG));
+    uint64_t sec = L.state(s);
+    for_each_field(ring[s], [&](float* dev, int comps) {
+      put(dev, comps, sec);
+      sec += L.field_bytes(comps);
+    });
   }
   {  // prev: owned cells only (check_evolution copies S() -> prev over [0, N))
-    const uint64_t b = L.state(3), c0 = topo.c0;
-    auto own = [&](void* dev, int comps, uint64_t sec) {
+    uint64_t sec = L.state(3);
+    const uint64_t c0 = topo.c0;
+    for_each_field(prev, [&](float* dev, int comps) {
       CFD_HIP(hipMemcpyAsync(dev, base + sec + c0 * comps * 4, (size_t)N * comps * 4, hipMemcpyHostToDevice, stream));
       sync();
-    };
-    own(prev.u, 2, b + Layout::u_off(NG));
-    own(prev.p, 1, b + Layout::p_off(NG));
-    own(prev.dp, 1, b + Layout::dp_off(NG));
-    own(prev.gp, 2, b + Layout::gp_off(NG));
+      sec += L.field_bytes(comps);
+    });
   }
   put(x, 3, L.x());
   if (h.amg_nnz) {
@@ -267,9 +263,7 @@ void Solver::load_state(const char* path) {
   step_index = (h.step_index + 2) % 3;  // rotate() advances it back to the saved slot triple
   rotate();
   have_prev = h.have_prev != 0;
-  inner = LagReader{};
-  inner.has_last = h.inner_has_last != 0;
-  inner.last = h.inner_last;
+  inner.restore(h.inner_has_last != 0, h.inner_last);  // a pending read belongs to the replaced state
   variance_history.clear();
   for (uint32_t k = 0; k < h.n_variance; ++k) variance_history.push_back({h.variance[k][0], h.variance[k][1]});
   constants = h.constants;

@@ -62,7 +62,7 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
     check_launch("flow diagnostics (fields)");
     return;
   }
-  launch_evolution_final(combine_d(diag_partial, kFlowDiagSums, diag_red_local, diag_red_gather),
+  launch_evolution_final(combine(diag_partial, kFlowDiagSums, diag_red_local, diag_red_gather),
                          reinterpret_cast<double*>(diag_res), stream);
   if (dist()) {
     const CommScope scope(this, kCommReduceGather);

@@ -152,7 +152,7 @@ void Solver::scalar_stats(int field, cfd_scalar_stats* out) {
   a.partial = sc_partial;
   a.blockmm = sc_blockmax;
   launch_scalar_stats(a, sc_res + 2, stream);
-  launch_evolution_final(combine_d(sc_partial, 1), reinterpret_cast<double*>(sc_res + 4), stream);
+  launch_evolution_final(combine(sc_partial, 1), reinterpret_cast<double*>(sc_res + 4), stream);
   check_launch("scalar stats");
   uint32_t h[8];
   CFD_HIP(hipMemcpyAsync(h, sc_res, sizeof(h), hipMemcpyDeviceToHost, stream));
