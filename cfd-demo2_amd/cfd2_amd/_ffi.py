@@ -180,6 +180,29 @@ class ScalarStats(C.Structure):  # cfd_scalar_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScalarSolver(C.Structure):  # cfd_scalar_solver
+    _fields_ = [
+        ("method", C.c_int32),
+        ("max_iters", C.c_int32),
+        ("check_interval", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class ScalarSolverStats(C.Structure):  # cfd_scalar_solver_stats
+    _fields_ = [
+        ("method", C.c_int32),
+        ("iterations", C.c_int32),
+        ("stop_reason", C.c_int32),
+        ("polish_sweeps", C.c_uint32),
+        ("krylov_residual", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     _fields_ = [
         ("magic", C.c_char * 8),
@@ -248,6 +271,7 @@ EXPORTED = [
     "cfd_adaptive_dt_rule", "cfd_adapt_dt", "cfd_group_flow_diagnostics", "cfd_group_adapt_dt",
     "cfd_scalar_config_default", "cfd_scalars_enable", "cfd_set_scalar_params", "cfd_set_scalar", "cfd_get_scalar",
     "cfd_scalar_advance", "cfd_scalar_stats_get",
+    "cfd_scalar_solver_default", "cfd_set_scalar_solver", "cfd_scalar_solver_stats_get",
 ]
 
 _lib = None

@@ -115,6 +115,10 @@ def _bind():
     L.cfd_get_scalar.argtypes = [_vp, C.c_int32, dp]
     L.cfd_scalar_advance.argtypes = [_vp, C.c_float]
     L.cfd_scalar_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarStats)]
+    L.cfd_scalar_solver_default.argtypes = [C.POINTER(_ffi.ScalarSolver)]
+    L.cfd_scalar_solver_default.restype = None
+    L.cfd_set_scalar_solver.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSolver)]
+    L.cfd_scalar_solver_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSolverStats)]
     _bound = True
     return L
 
@@ -367,6 +371,28 @@ class GpuSolver:
         self._call("cfd_scalar_stats_get", int(field), C.byref(st))
         return st
 
+    def set_scalar_solver(self, field, method="bicgstab", max_iters=None, check_interval=None) -> None:
+        """cfd_set_scalar_solver: ``method`` "jacobi" (0, the default of every
+        field) or "bicgstab" (1): BiCGStab on the Jacobi-scaled system, then
+        the Jacobi loop from its answer, which decides ``converged`` as before.
+        BiCGStab is for diffusion-dominated fields on fine meshes (D dt / h^2
+        well above 1: a temperature), where Jacobi needs thousands of sweeps; a
+        dye (D dt / h^2 below 1) converges in a few Jacobi sweeps and gains
+        nothing.  Unset options keep cfd_scalar_solver_default's values."""
+        cfg = scalar_solver_default()
+        methods = {"jacobi": 0, "bicgstab": 1}
+        cfg.method = methods[method] if method in methods else int(method)
+        if max_iters is not None:
+            cfg.max_iters = int(max_iters)
+        if check_interval is not None:
+            cfg.check_interval = int(check_interval)
+        self._call("cfd_set_scalar_solver", int(field), C.byref(cfg))
+
+    def scalar_solver_stats(self, field) -> _ffi.ScalarSolverStats:
+        st = _ffi.ScalarSolverStats()
+        self._call("cfd_scalar_solver_stats_get", int(field), C.byref(st))
+        return st
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -515,6 +541,13 @@ class GpuSolver:
         return out
 
 
+def scalar_solver_default() -> _ffi.ScalarSolver:
+    """cfd_scalar_solver_default (no handle and no GPU needed)."""
+    cfg = _ffi.ScalarSolver()
+    _bind().cfd_scalar_solver_default(C.byref(cfg))
+    return cfg
+
+
 def scalar_config_default() -> _ffi.ScalarConfig:
     """cfd_scalar_config_default (no handle and no GPU needed)."""
     cfg = _ffi.ScalarConfig()
@@ -571,7 +604,7 @@ class GpuGroup:
         # setters / state writers apply to every rank
         if name.startswith("set_") or name in ("update_constants", "initialize_history",
                                                "profile_enable", "profile_reset", "synchronize",
-                                               "enable_scalars"):  # refused by every rank: one GPU only
+                                               "enable_scalars", "scalar_solver_stats"):  # scalars: refused by every rank, one GPU only
             def f(*a, **k):
                 for r in self.ranks:
                     getattr(r, name)(*a, **k)

@@ -577,6 +577,39 @@ struct ScalarStatsArgs {
   uint32_t* blockmm;   // [2 * flow_diag_blocks(N)] scratch
 };
 void launch_scalar_stats(const ScalarStatsArgs& a, uint32_t* mm, hipStream_t s);
+// BiCGStab on the Jacobi-scaled system of the assembled field (include/
+// cfd2_amd.h "Arithmetic of method 1" is the contract).  The operator and the
+// x / r update run over blocks of 4 chunks (thread t of block b: cells b*1024
+// + q*256 + t, as k_scalar_stats) and leave the unit partials of their dots in
+// partial[v * np + unit] and the block maxima of |r| in blockmax; one-block
+// finishing kernels turn them into the coefficients and the status words.
+// Everything after a stop returns at once: x is frozen.
+constexpr uint32_t kKryDone = 0, kKryReason = 1, kKryIter = 2, kKryRes = 3, kKryMode = 4;  // state words
+struct ScalarKrylovArgs {
+  uint32_t N;
+  uint32_t ld;
+  const int32_t* other;   // fs.other
+  const uint32_t* nface;  // fs.nface
+  const float* coef;
+  const float* diag;
+  const float* b;
+  float* x;               // [N] phi_old on entry, the frozen iterate after the stop
+  float *rh, *r, *p, *v, *s, *t;  // [N] work vectors
+  uint32_t U;             // chunks per unit (RedGeom::U)
+  uint32_t np;            // unit partials per dot
+  double* partial;        // [2 * np]
+  uint32_t* blockmax;     // [flow_diag_blocks(N)]
+  double* dv;             // [4] rho, alpha, omega in f64
+  uint32_t* st;           // [8] done, reason, iteration, bits of max |r|, mode of the x / r update
+  float* co;              // [4] alpha, omega, beta rounded to f32
+  RedSrcD red;            // combine(partial, 2)
+  float tol;
+};
+// r = rh = p = J(x) - x, rho, max |r|; the state words (stop with reason 1 at
+// iteration 0 if max |r| <= tol)
+void launch_scalar_krylov_start(const ScalarKrylovArgs& a, hipStream_t s);
+// iteration k (1-based) and, for k < max_iters, the beta and p of iteration k + 1
+void launch_scalar_krylov_iteration(const ScalarKrylovArgs& a, uint32_t k, uint32_t max_iters, hipStream_t s);
 // key of an f32 bit pattern: increasing in the value over every non-NaN float
 __host__ __device__ inline uint32_t scalar_value_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
 __host__ __device__ inline uint32_t scalar_key_value(uint32_t key) { return (key & 0x80000000u) ? key & 0x7FFFFFFFu : ~key; }

@@ -188,7 +188,307 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
   }
 }
 
+// ---- BiCGStab on the Jacobi-scaled system (kernels.hpp ScalarKrylovArgs) ----
+// The matrix streams (columns, coefficients, diag, b) are read once per pass
+// and are larger than the Infinity Cache at the sizes this solver is for: they
+// are loaded nontemporally so the work vectors keep their lines.  Same bits.
+#ifndef CFD_SCALAR_KRYLOV_NT
+#define CFD_SCALAR_KRYLOV_NT 1
+#endif
+constexpr bool kKryNT = CFD_SCALAR_KRYLOV_NT != 0;
+constexpr int kKryInit = 0, kKryV = 1, kKryT = 2;
+
+__device__ __forceinline__ uint32_t abs_bits(float v) {
+  const float d = fabsf(v);
+  return d == d ? __float_as_uint(d) : kDeltaNaN;
+}
+
+// the block's unit partials of dot v from its quarter values l[chunk q][quarter w]
+__device__ __forceinline__ void kry_units(const ScalarKrylovArgs& a, const double (*l)[4], uint32_t lb, uint32_t v) {
+  const uint32_t U = a.U, UB = 4 / U;
+  if (threadIdx.x < UB) {
+    const uint32_t u = threadIdx.x, unit = lb * UB + u;
+    double ch[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ch[q] = (l[q][0] + l[q][1]) + (l[q][2] + l[q][3]);
+    const double val = unit_value(ch, U, u);
+    if ((uint64_t)unit * U * kRedChunkCells < a.N && unit < a.np) a.partial[(size_t)v * a.np + unit] = val;
+  }
+}
+
+// One operator pass with its dots.  kKryInit: r = rh = p = J(x) - x, <r, r>,
+// the block maximum of |r|.  kKryV: v = A p, <rh, v>.  kKryT: t = A s, <t, s>,
+// <t, t>.  The slots four at a time as k_scalar_sweep takes them.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_scalar_krylov_op(ScalarKrylovArgs a) {
+  __shared__ double lsum[2][4][4];  // [dot][chunk q][quarter w]
+  __shared__ uint32_t lmax[kBlock / 64];
+  if (MODE != kKryInit && a.st[kKryDone]) return;
+  const uint32_t N = a.N;
+  const uint32_t lb = xcd_block();
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* __restrict__ in = MODE == kKryInit ? a.x : (MODE == kKryV ? a.p : a.s);
+  float* __restrict__ out = MODE == kKryInit ? a.r : (MODE == kKryV ? a.v : a.t);
+  uint32_t bits = 0;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kStatCells + q * kRedChunkCells + threadIdx.x;
+    double t0 = 0.0, t1 = 0.0;
+    if (ci < N) {
+      const uint32_t i = (uint32_t)ci;
+      float sum = MODE == kKryInit ? ldx<kKryNT>(a.b + i) : 0.0f;
+      const float dg = ldx<kKryNT>(a.diag + i);
+      const uint32_t nf = a.nface[i];
+      for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
+        int32_t o[4];
+        float c[4], g[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t k = k0 + j;
+          const bool on = k < nf;
+          o[j] = on ? ldx<kKryNT>(a.other + ((size_t)k * N + i)) : kNoCell;
+          c[j] = on ? ldx<kKryNT>(a.coef + ((size_t)k * a.ld + i)) : 0.0f;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) g[j] = o[j] != kNoCell ? in[o[j]] : 0.0f;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+          if (o[j] != kNoCell) sum += c[j] * g[j];  // boundary slots are skipped
+      }
+      const float qd = sum / dg;
+      const float own = in[i];
+      const float res = MODE == kKryInit ? qd - own : own - qd;
+      out[i] = res;
+      if constexpr (MODE == kKryInit) {
+        a.rh[i] = res;
+        a.p[i] = res;
+        t0 = (double)res * (double)res;
+        const uint32_t ab = abs_bits(res);
+        bits = ab > bits ? ab : bits;
+      } else if constexpr (MODE == kKryV) {
+        t0 = (double)a.rh[i] * (double)res;
+      } else {
+        t0 = (double)res * (double)own;
+        t1 = (double)res * (double)res;
+      }
+    }
+    const double r0 = wave_tree(t0);
+    if (lane == 0) lsum[0][q][w] = r0;
+    if constexpr (MODE == kKryT) {
+      const double r1 = wave_tree(t1);
+      if (lane == 0) lsum[1][q][w] = r1;
+    }
+  }
+  if constexpr (MODE == kKryInit) {
+    bits = wave_max32(bits);
+    if (lane == 0) lmax[w] = bits;
+  }
+  __syncthreads();
+  kry_units(a, lsum[0], lb, 0);
+  if constexpr (MODE == kKryT) kry_units(a, lsum[1], lb, 1);
+  if constexpr (MODE == kKryInit) {
+    if (threadIdx.x == 64) {
+      const uint32_t m01 = lmax[0] > lmax[1] ? lmax[0] : lmax[1];
+      const uint32_t m23 = lmax[2] > lmax[3] ? lmax[2] : lmax[3];
+      a.blockmax[lb] = m01 > m23 ? m01 : m23;
+    }
+  }
+}
+
+// s = r - alpha v
+__global__ void __launch_bounds__(kBlock) k_scalar_krylov_s(ScalarKrylovArgs a) {
+  if (a.st[kKryDone]) return;
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.N) return;
+  const float alpha = a.co[0];
+  a.s[i] = a.r[i] - alpha * a.v[i];
+}
+
+// mode 0: x = (x + alpha p) + omega s, r = s - omega t; mode 1 (<t, t> == 0):
+// x = x + alpha p, r = s; mode 2: nothing.  With <rh, r> and the block maxima of |r|.
+__global__ void __launch_bounds__(kBlock) k_scalar_krylov_xr(ScalarKrylovArgs a) {
+  __shared__ double lsum[4][4];
+  __shared__ uint32_t lmax[kBlock / 64];
+  const uint32_t mode = a.st[kKryMode];
+  if (mode == 2u) return;
+  const uint32_t N = a.N;
+  const uint32_t lb = xcd_block();
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float alpha = a.co[0], omega = a.co[1];
+  uint32_t bits = 0;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kStatCells + q * kRedChunkCells + threadIdx.x;
+    double t0 = 0.0;
+    if (ci < N) {
+      const uint32_t i = (uint32_t)ci;
+      const float si = a.s[i];
+      float xn = a.x[i] + alpha * a.p[i];
+      float rn = si;
+      if (mode == 0u) {
+        xn = xn + omega * si;
+        rn = si - omega * a.t[i];
+      }
+      a.x[i] = xn;
+      a.r[i] = rn;
+      t0 = (double)a.rh[i] * (double)rn;
+      const uint32_t ab = abs_bits(rn);
+      bits = ab > bits ? ab : bits;
+    }
+    const double r0 = wave_tree(t0);
+    if (lane == 0) lsum[q][w] = r0;
+  }
+  bits = wave_max32(bits);
+  if (lane == 0) lmax[w] = bits;
+  __syncthreads();
+  kry_units(a, lsum, lb, 0);
+  if (threadIdx.x == 64) {
+    const uint32_t m01 = lmax[0] > lmax[1] ? lmax[0] : lmax[1];
+    const uint32_t m23 = lmax[2] > lmax[3] ? lmax[2] : lmax[3];
+    a.blockmax[lb] = m01 > m23 ? m01 : m23;
+  }
+}
+
+// p = r + beta (p - omega v)
+__global__ void __launch_bounds__(kBlock) k_scalar_krylov_p(ScalarKrylovArgs a) {
+  if (a.st[kKryDone]) return;
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.N) return;
+  const float omega = a.co[1], beta = a.co[2];
+  a.p[i] = a.r[i] + beta * (a.p[i] - omega * a.v[i]);
+}
+
+template <int NT>
+__device__ __forceinline__ uint32_t block_max32(const uint32_t* __restrict__ v, uint32_t nb, uint32_t* l) {
+  uint32_t m = 0;
+  for (uint32_t b = threadIdx.x; b < nb; b += NT) m = v[b] > m ? v[b] : m;
+  m = wave_max32(m);
+  if ((threadIdx.x & 63) == 0) l[threadIdx.x >> 6] = m;
+  __syncthreads();
+  uint32_t r = 0;
+  for (uint32_t w = 0; w < NT / 64; ++w) r = l[w] > r ? l[w] : r;
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ bool kry_bad(double v) { return v == 0.0 || !isfinite(v); }
+__device__ __forceinline__ bool kry_bad(float v) { return v == 0.0f || !isfinite(v); }
+__device__ __forceinline__ void kry_stop(uint32_t* st, uint32_t reason, uint32_t iter) {
+  st[kKryDone] = 1u;
+  st[kKryReason] = reason;
+  st[kKryIter] = iter;
+}
+
+// One block finishes a stage: the totals of its dots by the segment and total
+// trees, the coefficient in f64 and rounded to f32, the status words.
+constexpr int kKryFinStart = 0, kKryFinAlpha = 1, kKryFinOmega = 2, kKryFinBeta = 3;
+template <int STAGE>
+__global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKrylovArgs a, uint32_t nb, uint32_t k,
+                                                                        uint32_t max_iters) {
+  __shared__ double la[kRedMaxSegments], lb[65];
+  __shared__ uint32_t lm[kRedFinalThreads / 64];
+  uint32_t* st = a.st;
+  const uint32_t done = STAGE == kKryFinStart ? 0u : st[kKryDone];
+  const uint32_t mode = STAGE == kKryFinBeta ? st[kKryMode] : 0u;
+  __syncthreads();  // every thread has read the words thread 0 writes below
+  if constexpr (STAGE == kKryFinStart) {
+    const uint32_t res = block_max32<kRedFinalThreads>(a.blockmax, nb, lm);
+    const double rho = red_total<double, kRedFinalThreads>(a.red, 0, la, lb);
+    if (threadIdx.x == 0) {
+      const bool stop = __uint_as_float(res) <= a.tol;
+      st[kKryDone] = stop ? 1u : 0u;
+      st[kKryReason] = stop ? 1u : 0u;
+      st[kKryIter] = 0u;
+      st[kKryRes] = res;
+      st[kKryMode] = 2u;
+      a.dv[0] = rho;
+      a.dv[1] = a.dv[2] = 0.0;
+      a.co[0] = a.co[1] = a.co[2] = 0.0f;
+    }
+  } else if constexpr (STAGE == kKryFinAlpha) {
+    if (done) return;
+    const double d = red_total<double, kRedFinalThreads>(a.red, 0, la, lb);
+    if (threadIdx.x == 0) {
+      const double rho = a.dv[0];
+      const double alpha = rho / d;
+      const float af = (float)alpha;
+      if (kry_bad(rho) || kry_bad(d) || kry_bad(af)) {
+        kry_stop(st, 2u, k);
+        a.co[0] = 0.0f;
+      } else {
+        a.dv[1] = alpha;
+        a.co[0] = af;
+      }
+    }
+  } else if constexpr (STAGE == kKryFinOmega) {
+    if (done) {
+      if (threadIdx.x == 0) st[kKryMode] = 2u;
+      return;
+    }
+    const double ts = red_total<double, kRedFinalThreads>(a.red, 0, la, lb);
+    const double tt = red_total<double, kRedFinalThreads>(a.red, 1, la, lb);
+    if (threadIdx.x == 0) {
+      if (tt == 0.0) {
+        kry_stop(st, 2u, k);
+        st[kKryMode] = 1u;
+        a.co[1] = 0.0f;
+      } else {
+        const double omega = ts / tt;
+        const float of = (float)omega;
+        if (!isfinite(tt) || kry_bad(of)) {
+          kry_stop(st, 2u, k);
+          st[kKryMode] = 2u;
+          a.co[1] = 0.0f;
+        } else {
+          st[kKryMode] = 0u;
+          a.dv[2] = omega;
+          a.co[1] = of;
+        }
+      }
+    }
+  } else {
+    if (mode == 2u) return;  // this iteration stopped before its x / r update
+    const uint32_t res = block_max32<kRedFinalThreads>(a.blockmax, nb, lm);
+    const double rho1 = red_total<double, kRedFinalThreads>(a.red, 0, la, lb);
+    if (threadIdx.x == 0) {
+      st[kKryRes] = res;
+      if (done) return;  // mode 1: the stop is already recorded
+      if (__uint_as_float(res) <= a.tol) {
+        kry_stop(st, 1u, k);
+        return;
+      }
+      if (k >= max_iters) return;  // the host records reason 3
+      const double beta = (rho1 / a.dv[0]) * (a.dv[1] / a.dv[2]);
+      const float bf = (float)beta;
+      if (kry_bad(rho1) || kry_bad(bf)) {
+        kry_stop(st, 2u, k + 1u);
+        a.co[2] = 0.0f;
+      } else {
+        a.dv[0] = rho1;
+        a.co[2] = bf;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+void launch_scalar_krylov_start(const ScalarKrylovArgs& a, hipStream_t s) {
+  const uint32_t nb = flow_diag_blocks(a.N);
+  if (nb) hipLaunchKernelGGL((k_scalar_krylov_op<kKryInit>), dim3(nb), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((k_scalar_krylov_fin<kKryFinStart>), dim3(1), dim3(kRedFinalThreads), 0, s, a, nb, 0u, 0u);
+}
+
+void launch_scalar_krylov_iteration(const ScalarKrylovArgs& a, uint32_t k, uint32_t max_iters, hipStream_t s) {
+  const uint32_t nb = flow_diag_blocks(a.N), ne = grid_for(a.N);
+  if (!nb) return;
+  const dim3 one(1), fin(kRedFinalThreads), blk(kBlock);
+  hipLaunchKernelGGL((k_scalar_krylov_op<kKryV>), dim3(nb), blk, 0, s, a);
+  hipLaunchKernelGGL((k_scalar_krylov_fin<kKryFinAlpha>), one, fin, 0, s, a, nb, k, max_iters);
+  hipLaunchKernelGGL(k_scalar_krylov_s, dim3(ne), blk, 0, s, a);
+  hipLaunchKernelGGL((k_scalar_krylov_op<kKryT>), dim3(nb), blk, 0, s, a);
+  hipLaunchKernelGGL((k_scalar_krylov_fin<kKryFinOmega>), one, fin, 0, s, a, nb, k, max_iters);
+  hipLaunchKernelGGL(k_scalar_krylov_xr, dim3(nb), blk, 0, s, a);
+  hipLaunchKernelGGL((k_scalar_krylov_fin<kKryFinBeta>), one, fin, 0, s, a, nb, k, max_iters);
+  if (k < max_iters) hipLaunchKernelGGL(k_scalar_krylov_p, dim3(ne), blk, 0, s, a);
+}
 
 uint32_t scalar_sweep_blocks(uint32_t N) { return grid_for(N); }
 

@@ -578,6 +578,28 @@ cfd_status cfd_scalar_stats_get(cfd_solver* s, int32_t field, cfd_scalar_stats* 
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
   return guard([&] { s->s->scalar_stats(field, out); });
 }
+void cfd_scalar_solver_default(cfd_scalar_solver* c) {
+  if (!c) return;
+  c->method = 0;
+  c->max_iters = 500;
+  c->check_interval = 8;
+  c->reserved = 0;
+}
+cfd_status cfd_set_scalar_solver(cfd_solver* s, int32_t field, const cfd_scalar_solver* cfg) {
+  CHECK_S(s);
+  if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar solver config");
+  return guard([&] { s->s->set_scalar_solver(field, *cfg); });
+}
+cfd_status cfd_scalar_solver_stats_get(cfd_solver* s, int32_t field, cfd_scalar_solver_stats* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] {
+    if (s->s->dist())
+      throw std::invalid_argument("passive scalars run on one GPU only: no scalar solver on a distributed handle");
+    s->s->scalar_check(field);
+    *out = s->s->sc_field[field].kstats;
+  });
+}
 
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {

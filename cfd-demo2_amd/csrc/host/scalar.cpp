@@ -1,7 +1,8 @@
 // Passive scalar transport (include/cfd2_amd.h, the last section; kernels.hpp
 // "scalar.hip"): per advance and field one face-slot assembly from flux_s as
 // the last k_prepare left it, then Jacobi sweeps in batches of check_interval,
-// the host reading the last sweep's delta after each batch.
+// the host reading the last sweep's delta after each batch.  A field on method
+// 1 runs BiCGStab between the two and starts the sweeps from its answer.
 #include <cmath>
 #include <cstring>
 
@@ -26,6 +27,8 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   sc_alt = sc_coef = sc_diag = sc_b = nullptr;
   sc_blockmax = sc_res = nullptr;
   sc_partial = nullptr;
+  for (float*& v : kr_vec) v = nullptr;
+  kr_partial = kr_state = nullptr;
   for (ScalarField& f : sc_field) f = ScalarField{};
   if (count == 0) return;
   const size_t ld = topo.ld;
@@ -83,8 +86,6 @@ void Solver::scalar_advance(float dt) {
   }
   const Range range("scalar advance");
   CFD_HIP(hipSetDevice(device));
-  const uint32_t ci = (uint32_t)sc_cfg.check_interval;
-  const uint32_t max_sweeps = ((uint32_t)sc_cfg.max_sweeps + ci - 1) / ci * ci;
   for (int fi = 0; fi < sc_count; ++fi) {
     ScalarField& f = sc_field[fi];
     ScalarAssembleArgs A{};
@@ -103,40 +104,117 @@ void Solver::scalar_advance(float dt) {
     A.b = sc_b;
     launch_scalar_assemble(A, stream);
     check_launch("scalar assemble");
-    ScalarSweepArgs W{};
-    W.N = N;
-    W.ld = topo.ld;
-    W.other = fs.other;
-    W.nface = fs.nface;
-    W.coef = sc_coef;
-    W.diag = sc_diag;
-    W.b = sc_b;
-    W.blockmax = sc_blockmax;
     f.sweeps = 0;
     f.converged = 0;
     f.dt_used = dt;
-    uint32_t bits = 0;
-    while (f.sweeps < max_sweeps) {
-      for (uint32_t k = 0; k < ci; ++k) {  // phi^0 = phi_old; b holds a_t * phi_old, so its buffer is free to swap
-        W.phi_in = f.phi;
-        W.phi_out = sc_alt;
-        launch_scalar_sweep(W, k + 1 == ci ? sc_res : nullptr, stream);
-        std::swap(f.phi, sc_alt);
-      }
-      check_launch("scalar sweep");
-      CFD_HIP(hipMemcpyAsync(&bits, sc_res, sizeof(bits), hipMemcpyDeviceToHost, stream));
-      sync();
-      f.sweeps += ci;
-      std::memcpy(&f.last_delta, &bits, 4);
-      if (!std::isfinite(f.last_delta))
-        throw std::domain_error("scalar field " + std::to_string(fi) + " diverged: non-finite Jacobi update after " +
-                                std::to_string(f.sweeps) + " sweeps");
-      if (f.last_delta <= sc_cfg.tol) {
-        f.converged = 1;
-        break;
-      }
+    f.kstats = cfd_scalar_solver_stats{};
+    f.kstats.method = f.solver.method;
+    if (f.solver.method == 1) scalar_krylov(f);
+    scalar_polish(fi, f);
+    if (f.solver.method == 1) f.kstats.polish_sweeps = f.sweeps;
+  }
+}
+
+// The Jacobi loop from f.phi, in batches of check_interval sweeps.
+void Solver::scalar_polish(int fi, ScalarField& f) {
+  const uint32_t ci = (uint32_t)sc_cfg.check_interval;
+  const uint32_t max_sweeps = ((uint32_t)sc_cfg.max_sweeps + ci - 1) / ci * ci;
+  ScalarSweepArgs W{};
+  W.N = N;
+  W.ld = topo.ld;
+  W.other = fs.other;
+  W.nface = fs.nface;
+  W.coef = sc_coef;
+  W.diag = sc_diag;
+  W.b = sc_b;
+  W.blockmax = sc_blockmax;
+  uint32_t bits = 0;
+  while (f.sweeps < max_sweeps) {
+    for (uint32_t k = 0; k < ci; ++k) {  // phi^0 = phi_old; b holds a_t * phi_old, so its buffer is free to swap
+      W.phi_in = f.phi;
+      W.phi_out = sc_alt;
+      launch_scalar_sweep(W, k + 1 == ci ? sc_res : nullptr, stream);
+      std::swap(f.phi, sc_alt);
+    }
+    check_launch("scalar sweep");
+    CFD_HIP(hipMemcpyAsync(&bits, sc_res, sizeof(bits), hipMemcpyDeviceToHost, stream));
+    sync();
+    f.sweeps += ci;
+    std::memcpy(&f.last_delta, &bits, 4);
+    if (!std::isfinite(f.last_delta))
+      throw std::domain_error("scalar field " + std::to_string(fi) + " diverged: non-finite Jacobi update after " +
+                              std::to_string(f.sweeps) + " sweeps");
+    if (f.last_delta <= sc_cfg.tol) {
+      f.converged = 1;
+      break;
     }
   }
+}
+
+// BiCGStab on the Jacobi-scaled system (include/cfd2_amd.h "Arithmetic of
+// method 1"), x in place in f.phi: iterations in batches of the field's
+// check_interval, one read of the four status words per batch.  Every kernel
+// returns at once after the device recorded a stop, so the batch size changes
+// nothing but the number of reads.
+void Solver::scalar_krylov(ScalarField& f) {
+  ScalarKrylovArgs K{};
+  K.N = N;
+  K.ld = topo.ld;
+  K.other = fs.other;
+  K.nface = fs.nface;
+  K.coef = sc_coef;
+  K.diag = sc_diag;
+  K.b = sc_b;
+  K.x = f.phi;
+  K.rh = kr_vec[0];
+  K.r = kr_vec[1];
+  K.p = kr_vec[2];
+  K.v = kr_vec[3];
+  K.s = kr_vec[4];
+  K.t = kr_vec[5];
+  K.U = red.U;
+  K.np = pstride;
+  K.partial = kr_partial;
+  K.blockmax = sc_blockmax;
+  K.dv = kr_state;
+  K.st = reinterpret_cast<uint32_t*>(kr_state + 4);
+  K.co = reinterpret_cast<float*>(kr_state + 8);
+  K.red = combine(kr_partial, 2);
+  K.tol = sc_cfg.tol;
+  uint32_t st[4] = {0, 0, 0, 0};
+  auto read = [&](const char* where) {
+    check_launch(where);
+    CFD_HIP(hipMemcpyAsync(st, K.st, sizeof(st), hipMemcpyDeviceToHost, stream));
+    sync();
+  };
+  launch_scalar_krylov_start(K, stream);
+  read("scalar krylov start");
+  const uint32_t cap = (uint32_t)f.solver.max_iters, ci = (uint32_t)f.solver.check_interval;
+  uint32_t k = 0;
+  while (!st[kKryDone] && k < cap) {
+    const uint32_t end = std::min(cap, k + ci);
+    while (k < end) launch_scalar_krylov_iteration(K, ++k, cap, stream);
+    read("scalar krylov iteration");
+  }
+  f.kstats.iterations = st[kKryDone] ? (int32_t)st[kKryIter] : (int32_t)cap;
+  f.kstats.stop_reason = st[kKryDone] ? (int32_t)st[kKryReason] : 3;
+  std::memcpy(&f.kstats.krylov_residual, &st[kKryRes], 4);
+}
+
+void Solver::set_scalar_solver(int field, const cfd_scalar_solver& c) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar solver on a distributed handle");
+  scalar_check(field);
+  if (c.method != 0 && c.method != 1) throw std::invalid_argument("scalar solver: method must be 0 (Jacobi) or 1 (BiCGStab)");
+  if (c.max_iters < 1) throw std::invalid_argument("scalar solver: max_iters must be >= 1");
+  if (c.check_interval < 1) throw std::invalid_argument("scalar solver: check_interval must be >= 1");
+  if (c.method == 1 && !kr_state) {
+    CFD_HIP(hipSetDevice(device));
+    for (float*& v : kr_vec) v = sc_arena.alloc<float>(topo.ld);
+    kr_partial = sc_arena.alloc<double>(2 * (size_t)pstride);
+    kr_state = sc_arena.alloc<double>(12);
+  }
+  sc_field[field].solver = c;
+  sc_field[field].solver.reserved = 0;
 }
 
 void Solver::scalar_stats(int field, cfd_scalar_stats* out) {

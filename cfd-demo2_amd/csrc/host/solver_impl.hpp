@@ -594,6 +594,8 @@ struct Solver {
     int32_t converged = 0;
     float last_delta = 0.0f;
     float dt_used = 0.0f;
+    cfd_scalar_solver solver{0, 500, 8, 0};  // cfd_scalar_solver_default
+    cfd_scalar_solver_stats kstats{};        // of the last advance
   };
   DeviceArena sc_arena;
   int sc_count = 0;
@@ -606,12 +608,20 @@ struct Solver {
   uint32_t* sc_blockmax = nullptr; // per-block scratch of the sweep's delta and the stats' min / max
   uint32_t* sc_res = nullptr;      // [0] delta bits, [2..3] min / max keys, [4..5] the integral (f64)
   double* sc_partial = nullptr;    // [pstride] unit partials of the integral
+  // BiCGStab work space, allocated in sc_arena by the first set_scalar_solver
+  // that selects method 1 (null before)
+  float* kr_vec[6] = {};           // [ld] each: rh, r, p, v, s, t
+  double* kr_partial = nullptr;    // [2 * pstride] unit partials of an iteration's dots
+  double* kr_state = nullptr;      // [0..3] rho, alpha, omega (f64); then 8 status words; then alpha, omega, beta (f32)
   float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
   void scalars_enable(int count, const cfd_scalar_config& c);
   void scalar_check(int field) const;  // throws std::invalid_argument: not enabled / bad index
   void set_scalar(int field, const double* phi);
   void get_scalar(int field, double* phi);
   void scalar_advance(float dt);
+  void set_scalar_solver(int field, const cfd_scalar_solver& c);
+  void scalar_krylov(ScalarField& f);   // the Krylov phase of one assembled field: f.phi becomes its frozen x
+  void scalar_polish(int fi, ScalarField& f);   // the Jacobi loop from f.phi: sweeps, last_delta, converged
   void scalar_stats(int field, cfd_scalar_stats* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver

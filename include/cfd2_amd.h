@@ -600,6 +600,76 @@ cfd_status cfd_get_scalar(cfd_solver* s, int32_t field, double* phi /* [N] */);
 cfd_status cfd_scalar_advance(cfd_solver* s, float dt);
 cfd_status cfd_scalar_stats_get(cfd_solver* s, int32_t field, cfd_scalar_stats* out);
 
+/* Solver of one scalar field.  Method 0 (the default) is the Jacobi loop
+ * above, unchanged.  Method 1 runs BiCGStab on the Jacobi-scaled system first
+ * and then the same Jacobi loop from its answer ("polish"), which alone
+ * decides `converged`: it is for fields whose diffusion dominates on a fine
+ * mesh (D dt / h^2 >> 1), where Jacobi needs thousands of sweeps.  A handle
+ * that never selects method 1 allocates and launches nothing new; the first
+ * selection allocates six work vectors, freed by cfd_scalars_enable(0).
+ *
+ * Arithmetic of method 1.  coef (c_k), diag and b are the assembled system
+ * above; J(x)_i = (b_i + sum_k c_k x[o_k]) / diag_i is one Jacobi sweep (the
+ * internal slots k in slot order, o_k the slot's neighbour, the sum starting
+ * from b_i, a true division).  Vectors are f32 and every vector operation is
+ * one f32 rounding per multiply, add, subtract or divide (nothing fused).
+ *   operator  (A v)_i = v_i - (sum_k c_k v[o_k]) / diag_i, the sum over the
+ *             internal slots in slot order starting from +0.0f
+ *   dots      <a, b> = the canonical sum (the tree of cfd_scalar_stats.
+ *             integral) of the f64 cell terms (double)a_i * (double)b_i
+ *   scalars   rho, alpha, omega, beta are f64 on the device; a vector
+ *             operation uses the f64 value rounded once to f32
+ *   start     x = phi_old; r = J(x) - x; rh = r; p = r; rho = <rh, r>;
+ *             res = max_i |r_i|.  res <= tol: stop, reason 1, iteration 0.
+ *   iteration k = 1, 2, ...:
+ *     a  v = A p;  d = <rh, v>;  alpha = rho / d.  If rho, d or f32(alpha) is
+ *        zero or not finite: stop, reason 2, iteration k, x untouched.
+ *     b  s = r - alpha v;  t = A s;  ts = <t, s>;  tt = <t, t>.
+ *        tt == 0: x = x + alpha p; r = s; res = max |r|; stop, reason 2,
+ *        iteration k.  Otherwise omega = ts / tt; if tt or f32(omega) is zero
+ *        or not finite: stop, reason 2, iteration k, x untouched.
+ *     c  x = (x + alpha p) + omega s;  r = s - omega t;  res = max_i |r_i|;
+ *        rho' = <rh, r>.  res <= tol: stop, reason 1, iteration k.
+ *        k == max_iters: stop, reason 3, iteration k.
+ *     d  (the first coefficient of iteration k + 1)
+ *        beta = (rho' / rho) * (alpha / omega), alpha and omega the f64
+ *        values.  If rho' or f32(beta) is zero or not finite: stop, reason 2,
+ *        iteration k + 1, x as step c left it.  Otherwise
+ *        p = r + beta (p - omega v);  rho = rho'.
+ *   max |r_i| is taken over f32 bit patterns, a NaN counting as +inf.
+ * After a stop nothing is written any more: x is frozen bit for bit.  The
+ * host launches iterations in batches of cfd_scalar_solver.check_interval and
+ * reads the status words after each batch; x, the iteration count and the
+ * reason do not depend on that interval.
+ *   polish    from the frozen x, the Jacobi loop of method 0 with the handle's
+ *             cfd_scalar_config: at least one batch of check_interval sweeps
+ *             runs, and cfd_scalar_stats.sweeps / converged / last_delta
+ *             describe it exactly as they describe method 0.  A non-finite
+ *             update is CFD_ERR_DIVERGED, running out of sweeps converged = 0.
+ * The iterates of the Krylov phase are not convex combinations; the final x
+ * of a converged advance satisfies x_i <= J(x)_i + tol, so a dye in [0, 1]
+ * stays within tol * max_i(diag_i / a_t,i) plus rounding of that interval.  */
+typedef struct cfd_scalar_solver {
+  int32_t method;          /* 0 Jacobi, 1 BiCGStab then Jacobi polish */
+  int32_t max_iters;       /* BiCGStab iteration cap; default 500; >= 1 */
+  int32_t check_interval;  /* iterations per host read; default 8; >= 1 */
+  int32_t reserved;
+} cfd_scalar_solver;
+typedef struct cfd_scalar_solver_stats {
+  int32_t method;          /* of the last cfd_scalar_advance, this field */
+  int32_t iterations;      /* the iteration the Krylov phase stopped in; 0 for method 0 */
+  int32_t stop_reason;     /* 1 residual, 2 breakdown, 3 max_iters; 0 for method 0 */
+  uint32_t polish_sweeps;  /* == cfd_scalar_stats.sweeps for method 1; 0 for method 0 */
+  float krylov_residual;   /* the last res of the Krylov phase (recursive residual) */
+  int32_t reserved;
+} cfd_scalar_solver_stats;
+void cfd_scalar_solver_default(cfd_scalar_solver* cfg); /* method 0, 500, 8 */
+/* Takes effect at the next cfd_scalar_advance.  CFD_ERR_INVALID: scalars not
+ * enabled, a bad field index, a method other than 0 or 1, max_iters < 1,
+ * check_interval < 1.  cfd_scalars_enable resets every field to method 0.   */
+cfd_status cfd_set_scalar_solver(cfd_solver* s, int32_t field, const cfd_scalar_solver* cfg);
+cfd_status cfd_scalar_solver_stats_get(cfd_solver* s, int32_t field, cfd_scalar_solver_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

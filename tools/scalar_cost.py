@@ -15,6 +15,14 @@ At each bench configuration (default c1 and c2), on one handle after 2 steps
 Writes profiles/r08/scalar_cost.json.
 
     python tools/scalar_cost.py [--configs c1 c2] [--mesh-cache-dir DIR]
+
+--krylov: instead, Jacobi against BiCGStab + polish (set_scalar_solver) for one
+field at dt = 1e-3, D = 1e-4 (a dye) and D = 0.01 (diffusion dominated), every
+advance from the same step profile: sweeps / iterations and the median of 5
+fenced calls each (Jacobi with max_sweeps raised until it converges); the time
+of one BiCGStab iteration as (128 iterations - 64 iterations) / 64 at tol = 0,
+its layout bytes over that time, and the sweep kernel's rate as in (b).
+Writes profiles/r09/scalar_krylov.json.
 """
 from __future__ import annotations
 
@@ -43,6 +51,60 @@ def sweep_layout_bytes(mesh) -> float:
     return 8.0 * slots + 16.0 * mesh.num_cells() + 4.0 * mesh.num_cells()
 
 
+def krylov_layout_bytes(mesh) -> float:
+    """Layout bytes of one BiCGStab iteration, each element of a pass once: the
+    two operator passes read every used slot's column and coefficient (16 B per
+    slot); per cell, 4 B each: v = A p: nface, diag, p, rh, v; s: r, v, s; t = A
+    s: nface, diag, s, t; x / r: x twice, p, s, t, rh, r; p: r, v, p twice (92 B)."""
+    slots = float(mesh.arrays()["cell_face_offsets"][-1])
+    return 16.0 * slots + 92.0 * mesh.num_cells()
+
+
+def krylov_rows(s, mesh, name, np):
+    x = mesh.arrays()["cell_cx"]
+    dye = np.where(x < 0.5, 1.0, 0.0)
+
+    def run(D, method, reps=5, **cfg):
+        kw = {k: cfg.pop(k) for k in ("max_iters", "check_interval_k") if k in cfg}
+        s.enable_scalars(1, **cfg)
+        s.set_scalar_params(0, D, 1.0)
+        if method:
+            s.set_scalar_solver(0, "bicgstab", max_iters=kw.get("max_iters"), check_interval=kw.get("check_interval_k"))
+        ts = []
+        for r in range(reps + 1):  # the first call is the warm-up
+            s.set_scalar(0, dye)
+            s.synchronize()
+            t0 = time.perf_counter()
+            s.advance_scalars()
+            s.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts[1:]), s.scalar_stats(0), s.scalar_solver_stats(0)
+
+    rows = []
+    for D in (1e-4, 0.01):
+        j_t, j_st, _ = run(D, False, max_sweeps=200000)
+        k_t, k_st, k_ks = run(D, True)
+        rows.append(dict(config=name, cells=mesh.num_cells(), dt=1e-3, diffusivity=D,
+                         jacobi_sweeps=int(j_st.sweeps), jacobi_converged=int(j_st.converged), jacobi_ms=1e3 * j_t,
+                         bicgstab_iterations=int(k_ks.iterations), bicgstab_reason=int(k_ks.stop_reason),
+                         polish_sweeps=int(k_ks.polish_sweeps), bicgstab_converged=int(k_st.converged),
+                         bicgstab_ms=1e3 * k_t, bicgstab_faster=bool(k_t < j_t)))
+    t64, _, k64 = run(0.01, True, tol=0.0, max_sweeps=4, max_iters=64, check_interval_k=64)
+    t128, _, k128 = run(0.01, True, tol=0.0, max_sweeps=4, max_iters=128, check_interval_k=128)
+    assert (k64.iterations, k128.iterations) == (64, 128), (k64.iterations, k128.iterations)
+    it_s = (t128 - t64) / 64
+    s.enable_scalars(1, max_sweeps=64, check_interval=64)
+    s.set_scalar_params(0, 0.01, 1.0)
+    s.set_scalar(0, dye)
+    s.advance_scalars()
+    b_med, _, _ = fenced(s, s.advance_scalars, reps=10)
+    kb, sb = krylov_layout_bytes(mesh), sweep_layout_bytes(mesh)
+    rate = dict(config=name, cells=mesh.num_cells(), iteration_us=1e6 * it_s, iteration_layout_bytes=kb,
+                iteration_gbs=kb / it_s / 1e9, sweep_us=1e6 * b_med / 64, sweep_layout_bytes=sb,
+                sweep_gbs=sb / (b_med / 64) / 1e9)
+    return rows, rate
+
+
 def fenced(solver, fn, reps=20):
     ts, sweeps = [], []
     for _ in range(reps):
@@ -59,13 +121,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c1", "c2"], choices=sorted(H))
     ap.add_argument("--mesh-cache-dir", default=None, help="load / save <dir>/<config>.mesh (bench.py --mesh-cache files)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "scalar_cost.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--krylov", action="store_true", help="Jacobi against BiCGStab (profiles/r09/scalar_krylov.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", *(("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")))
     import numpy as np
     from cfd2_amd import GpuSolver, build_id, default_config
     from cfd2_amd.mesh import Mesh, bench_channel
 
-    rows = []
+    rows, rates = [], []
     for name in args.configs:
         cache = os.path.join(args.mesh_cache_dir, name + ".mesh") if args.mesh_cache_dir else None
         if cache and os.path.exists(cache):
@@ -82,6 +147,17 @@ def main():
         s.set_alpha_p(0.3)
         s.set_precond_type(1)
         s.initialize_history()
+        if args.krylov:
+            s.step()
+            s.step()
+            r, rate = krylov_rows(s, mesh, name, np)
+            for row in r + [rate]:
+                print(json.dumps(row), flush=True)
+            rows += r
+            rates.append(rate)
+            s.close()
+            del mesh
+            continue
         s.profile_enable(True)
         s.step()           # includes the AMG setup
         s.profile_reset()  # the smoother's times of the second step only
@@ -118,6 +194,15 @@ def main():
         s.close()
         del mesh
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.krylov:
+        with open(args.out, "w") as fh:
+            json.dump(dict(what="one field, dt 1e-3, one handle after 2 steps, every advance from the same step profile "
+                                "(tools/scalar_cost.py --krylov): medians of 5 fenced advance_scalars() calls; Jacobi with "
+                                "max_sweeps raised to 200,000; rates: one BiCGStab iteration = (128 - 64 iterations) / 64 "
+                                "at tol 0, one sweep = 64 sweeps / 64, layout bytes with each element of a pass once",
+                           build=build_id(), rows=rows, rates=rates), fh, indent=1)
+            fh.write("\n")
+        return
     with open(args.out, "w") as fh:
         json.dump(dict(what="median of 20 fenced advance_scalars() calls for one field, one handle, after 2 steps "
                             "(tools/scalar_cost.py); advance_* = the default config (a whole host call: the assembly, "
