@@ -7,6 +7,6 @@ from . import mesh  # noqa: F401
 from .mesh import (BackwardsStep, ChannelWithObstacle, CircleObstacle, Mesh,  # noqa: F401
                    RectangularChannel, generate_cut_cell_mesh)
 from .solver import (GpuGroup, GpuSolver, adaptive_dt_rule, dist_plan, dist_unique_id,  # noqa: F401,E402
-                     scalar_config_default, scalar_solver_default)
-from ._ffi import (Config, Constants, FlowDiag, ScalarConfig, ScalarParams, ScalarSolver,  # noqa: F401,E402
-                   ScalarSolverStats, ScalarStats, build_id, default_config)
+                     scalar_config_default, scalar_scheme_default, scalar_solver_default)
+from ._ffi import (Config, Constants, FlowDiag, ScalarConfig, ScalarParams, ScalarScheme,  # noqa: F401,E402
+                   ScalarSchemeStats, ScalarSolver, ScalarSolverStats, ScalarStats, build_id, default_config)

@@ -203,6 +203,17 @@ class ScalarSolverStats(C.Structure):  # cfd_scalar_solver_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScalarScheme(C.Structure):  # cfd_scalar_scheme
+    _fields_ = [("scheme", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class ScalarSchemeStats(C.Structure):  # cfd_scalar_scheme_stats
+    _fields_ = [("scheme", C.c_int32), ("clamped_cells", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self) -> dict:
+        return {"scheme": self.scheme, "clamped_cells": self.clamped_cells}
+
+
 class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     _fields_ = [
         ("magic", C.c_char * 8),
@@ -272,6 +283,7 @@ EXPORTED = [
     "cfd_scalar_config_default", "cfd_scalars_enable", "cfd_set_scalar_params", "cfd_set_scalar", "cfd_get_scalar",
     "cfd_scalar_advance", "cfd_scalar_stats_get",
     "cfd_scalar_solver_default", "cfd_set_scalar_solver", "cfd_scalar_solver_stats_get",
+    "cfd_scalar_scheme_default", "cfd_set_scalar_scheme", "cfd_scalar_scheme_stats_get",
 ]
 
 _lib = None

@@ -119,6 +119,10 @@ def _bind():
     L.cfd_scalar_solver_default.restype = None
     L.cfd_set_scalar_solver.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSolver)]
     L.cfd_scalar_solver_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSolverStats)]
+    L.cfd_scalar_scheme_default.argtypes = [C.POINTER(_ffi.ScalarScheme)]
+    L.cfd_scalar_scheme_default.restype = None
+    L.cfd_set_scalar_scheme.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarScheme)]
+    L.cfd_scalar_scheme_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSchemeStats)]
     _bound = True
     return L
 
@@ -393,6 +397,24 @@ class GpuSolver:
         self._call("cfd_scalar_solver_stats_get", int(field), C.byref(st))
         return st
 
+    def set_scalar_scheme(self, field, scheme="vanleer") -> None:
+        """cfd_set_scalar_scheme: ``scheme`` "upwind" (0, the default of every
+        field) or "vanleer" (1, "limited linear"): a van Leer-limited
+        linear-upwind face value as a deferred correction on phi_old, clamped to
+        the local extrema of phi_old so a dye in [0, 1] stays there as under
+        upwind.  It costs one gradient pass and a wider assembly per advance
+        and keeps a front about half as wide at small CFL.  Takes effect at the
+        next advance_scalars()."""
+        cfg = scalar_scheme_default()
+        schemes = {"upwind": 0, "vanleer": 1}
+        cfg.scheme = schemes[scheme] if scheme in schemes else int(scheme)
+        self._call("cfd_set_scalar_scheme", int(field), C.byref(cfg))
+
+    def scalar_scheme_stats(self, field) -> _ffi.ScalarSchemeStats:
+        st = _ffi.ScalarSchemeStats()
+        self._call("cfd_scalar_scheme_stats_get", int(field), C.byref(st))
+        return st
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -548,6 +570,13 @@ def scalar_solver_default() -> _ffi.ScalarSolver:
     return cfg
 
 
+def scalar_scheme_default() -> _ffi.ScalarScheme:
+    """cfd_scalar_scheme_default (no handle and no GPU needed)."""
+    cfg = _ffi.ScalarScheme()
+    _bind().cfd_scalar_scheme_default(C.byref(cfg))
+    return cfg
+
+
 def scalar_config_default() -> _ffi.ScalarConfig:
     """cfd_scalar_config_default (no handle and no GPU needed)."""
     cfg = _ffi.ScalarConfig()
@@ -604,7 +633,7 @@ class GpuGroup:
         # setters / state writers apply to every rank
         if name.startswith("set_") or name in ("update_constants", "initialize_history",
                                                "profile_enable", "profile_reset", "synchronize",
-                                               "enable_scalars", "scalar_solver_stats"):  # scalars: refused by every rank, one GPU only
+                                               "enable_scalars", "scalar_solver_stats", "scalar_scheme_stats"):  # scalars: refused by every rank, one GPU only
             def f(*a, **k):
                 for r in self.ranks:
                     getattr(r, name)(*a, **k)

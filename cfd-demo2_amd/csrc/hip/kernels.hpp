@@ -543,6 +543,26 @@ struct ScalarAssembleArgs {
   float* b;              // [N]
 };
 void launch_scalar_assemble(const ScalarAssembleArgs& a, hipStream_t s);
+// Scheme 1, "limited linear" (include/cfd2_amd.h "Arithmetic of scheme 1" is
+// the contract): the Green-Gauss gradient of phi_old with the face values of
+// prepare_cell's vfu branch, then the assembly above with b_i = the clamped
+// a_t * phi_old_i - corr_i (+ the inlet terms).  coef and diag get the bits
+// launch_scalar_assemble writes.
+struct ScalarGradArgs {
+  uint32_t N;
+  FaceSlots fs;
+  const float* vol;
+  const float* phi_old;  // [N]
+  float inlet_value;
+  float2* g;             // [N]
+};
+void launch_scalar_grad(const ScalarGradArgs& a, hipStream_t s);
+struct ScalarLimitedArgs {
+  ScalarAssembleArgs a;
+  const float2* g;    // [N] launch_scalar_grad's, complete before this launch
+  uint32_t* clamped;  // one word: += the cells whose t the clamp changed (the caller zeroes it)
+};
+void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s);
 // One Jacobi sweep: phi_out_i = (b_i + sum over internal slots k of c_k *
 // phi_in[other_k]) / diag_i, the sum starting from b_i, a true division.  The
 // columns are fs.other as it stands (stride N).

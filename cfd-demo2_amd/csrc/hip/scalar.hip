@@ -1,7 +1,8 @@
 // Passive scalar transport (kernels.hpp "scalar.hip"): the face-slot assembly
 // of one field's implicit-Euler upwind system from the mass fluxes k_prepare
-// left in flux_s, one Jacobi sweep over its slot-major ELL image, and the
-// read-only field statistics.  Nothing the step reads is written.
+// left in flux_s (and, for a field on scheme 1, the gradient pass and the
+// limited right-hand side), one Jacobi sweep over its slot-major ELL image, and
+// the read-only field statistics.  Nothing the step reads is written.
 #include <hip/hip_runtime.h>
 
 #include "device_util.hpp"
@@ -46,6 +47,160 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a
   }
   a.diag[i] = diag;
   a.b[i] = b;
+}
+
+// ---- scheme 1, "limited linear" (kernels.hpp ScalarGradArgs / ScalarLimitedArgs) ----
+// The Green-Gauss gradient of phi_old, thread per cell: the face values of
+// prepare_cell's vfu branch (flux.hip), the slots four at a time as
+// k_scalar_sweep takes them (the coalesced slot loads, then the four gathers in
+// flight together), the sums in slot order; one 8-byte store.
+__global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
+  const uint32_t i = row_id();
+  const uint32_t N = a.N;
+  if (i >= N) return;
+  const FaceSlots fs = a.fs;
+  const float pc = a.phi_old[i];
+  const float vol = a.vol[i];
+  float gx = 0.0f, gy = 0.0f;
+  const uint32_t nf = fs.nface[i];
+  for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
+    int32_t o[4];
+    uint32_t mt[4];
+    float ar[4], nx[4], ny[4], lam[4], po[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const bool on = k0 + j < nf;
+      const size_t e = (size_t)(k0 + j) * N + i;
+      o[j] = on ? fs.other[e] : kNoCell;
+      mt[j] = on ? fs.meta[e] : 0u;
+      ar[j] = on ? fs.area[e] : 0.0f;
+      nx[j] = on ? fs.nx[e] : 0.0f;
+      ny[j] = on ? fs.ny[e] : 0.0f;
+      lam[j] = on ? fs.lam_s[e] : 0.0f;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) po[j] = o[j] != kNoCell ? a.phi_old[o[j]] : 0.0f;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      if (k0 + j >= nf) continue;  // an unused slot adds nothing, not even +0
+      float vf;
+      if (o[j] != kNoCell)
+        vf = (mt[j] & kMetaDegen) == 0 ? lam[j] * pc + (1.0f - lam[j]) * po[j] : 0.5f * (pc + po[j]);
+      else
+        vf = (mt[j] & kMetaBtypeMask) == 1u ? a.inlet_value : pc;
+      gx += vf * nx[j] * ar[j];
+      gy += vf * ny[j] * ar[j];
+    }
+  }
+  a.g[i] = make_float2(gx / vol, gy / vol);
+}
+
+// One slot's coefficient, the expression of k_scalar_assemble
+__device__ __forceinline__ float scalar_coef(float rd, float F, float area, float dist_e) {
+  const float diff = rd * area / dist_e;
+  const float cin = F < 0.0f ? -F : 0.0f;
+  return cin + diff;
+}
+
+// k_scalar_assemble with the limited right-hand side: the same coef and diag;
+// b_i = clamp(a_t phi_old_i - corr_i) + the inlet terms.  Per internal slot one
+// gather of phi_old[o] and, where the neighbour is the upwind cell, one 8-byte
+// gather of g[o].  The inlet products wait for the clamp: their slots are
+// remembered as a bit mask and their coefficients formed again afterwards
+// (the same expression, the same bits).  The block's clamped cells: a ballot
+// and a population count per wavefront, one atomic add per block.
+__global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimitedArgs q) {
+  __shared__ uint32_t lcnt[kBlock / 64];
+  const ScalarAssembleArgs& a = q.a;
+  const uint32_t i = row_id();
+  const uint32_t N = a.N;
+  bool clamped = false;
+  if (i < N) {
+    const FaceSlots fs = a.fs;
+    const float a_t = a.vol[i] * a.density / a.dt;
+    const float rd = a.density * a.diffusivity;
+    const float pc = a.phi_old[i];
+    const float2 gc = q.g[i];
+    float diag = a_t, corr = 0.0f, mn = pc, mx = pc;
+    uint32_t inlets = 0;  // bit k: slot k is an inlet slot (the host refuses wf > 32)
+    const uint32_t nf = fs.nface[i];
+    for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
+      int32_t o[4];
+      uint32_t mt[4];
+      float F[4], ar[4], de[4], dx[4], dy[4], po[4];
+      float2 go[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const bool on = k0 + j < nf;
+        const size_t e = (size_t)(k0 + j) * N + i;
+        o[j] = on ? fs.other[e] : kNoCell;
+        mt[j] = on ? fs.meta[e] : 0u;
+        F[j] = on ? a.flux_s[e] : 0.0f;
+        ar[j] = on ? fs.area[e] : 0.0f;
+        de[j] = on ? fs.dist_e[e] : 1.0f;
+        dx[j] = on ? fs.dvx[e] : 0.0f;
+        dy[j] = on ? fs.dvy[e] : 0.0f;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const bool in = o[j] != kNoCell;
+        po[j] = in ? a.phi_old[o[j]] : 0.0f;
+        go[j] = in && F[j] < 0.0f ? q.g[o[j]] : gc;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t k = k0 + j;
+        if (k >= nf) continue;
+        const uint32_t bt = mt[j] & kMetaBtypeMask;
+        const bool internal = o[j] != kNoCell;
+        const float c = internal || bt == 1u ? scalar_coef(rd, F[j], ar[j], de[j]) : 0.0f;
+        a.coef[(size_t)k * a.ld + i] = c;
+        diag += c;
+        if (internal) {
+          mn = po[j] < mn ? po[j] : mn;
+          mx = po[j] > mx ? po[j] : mx;
+          if (F[j] > 0.0f || F[j] < 0.0f) {
+            const bool own = F[j] > 0.0f;  // this cell is the upwind one
+            const float d = own ? po[j] - pc : pc - po[j];
+            const float2 gu = own ? gc : go[j];
+            const float dot = gu.x * dx[j] + gu.y * dy[j];
+            const float gd = own ? dot : -dot;
+            float h = 0.0f;
+            if (d != 0.0f) {
+              const float r = (2.0f * gd) / d - 1.0f;
+              const float psi = r > 0.0f ? 2.0f / (1.0f + 1.0f / r) : 0.0f;
+              h = (0.5f * psi) * d;
+            }
+            corr += F[j] * h;
+          }
+        } else if (bt == 1u) {
+          mn = a.inlet_value < mn ? a.inlet_value : mn;
+          mx = a.inlet_value > mx ? a.inlet_value : mx;
+          inlets |= 1u << k;
+        }
+      }
+    }
+    a.diag[i] = diag;
+    float t = a_t * pc - corr;
+    const float lo = a_t * mn, hi = a_t * mx;
+    clamped = t < lo || t > hi;
+    t = t < lo ? lo : (t > hi ? hi : t);
+    float b = t;
+    while (inlets) {
+      const uint32_t k = (uint32_t)__ffs((int)inlets) - 1u;
+      inlets &= inlets - 1u;
+      const size_t e = (size_t)k * N + i;
+      b += scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]) * a.inlet_value;
+    }
+    a.b[i] = b;
+  }
+  const unsigned long long votes = __ballot(clamped);
+  if ((threadIdx.x & 63) == 0) lcnt[threadIdx.x >> 6] = (uint32_t)__popcll(votes);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t n = (lcnt[0] + lcnt[1]) + (lcnt[2] + lcnt[3]);
+    if (n) atomicAdd(q.clamped, n);
+  }
 }
 
 __device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
@@ -495,6 +650,16 @@ uint32_t scalar_sweep_blocks(uint32_t N) { return grid_for(N); }
 void launch_scalar_assemble(const ScalarAssembleArgs& a, hipStream_t s) {
   if (!a.N) return;
   hipLaunchKernelGGL(k_scalar_assemble, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a);
+}
+
+void launch_scalar_grad(const ScalarGradArgs& a, hipStream_t s) {
+  if (!a.N) return;
+  hipLaunchKernelGGL(k_scalar_grad, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a);
+}
+
+void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s) {
+  if (!a.a.N) return;
+  hipLaunchKernelGGL(k_scalar_assemble_limited, dim3(grid_for(a.a.N)), dim3(kBlock), 0, s, a);
 }
 
 void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s) {

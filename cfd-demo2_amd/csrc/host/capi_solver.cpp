@@ -600,6 +600,20 @@ cfd_status cfd_scalar_solver_stats_get(cfd_solver* s, int32_t field, cfd_scalar_
     *out = s->s->sc_field[field].kstats;
   });
 }
+void cfd_scalar_scheme_default(cfd_scalar_scheme* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+}
+cfd_status cfd_set_scalar_scheme(cfd_solver* s, int32_t field, const cfd_scalar_scheme* cfg) {
+  CHECK_S(s);
+  if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar scheme config");
+  return guard([&] { s->s->set_scalar_scheme(field, *cfg); });
+}
+cfd_status cfd_scalar_scheme_stats_get(cfd_solver* s, int32_t field, cfd_scalar_scheme_stats* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->scalar_scheme_stats(field, out); });
+}
 
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {

@@ -2,7 +2,9 @@
 // "scalar.hip"): per advance and field one face-slot assembly from flux_s as
 // the last k_prepare left it, then Jacobi sweeps in batches of check_interval,
 // the host reading the last sweep's delta after each batch.  A field on method
-// 1 runs BiCGStab between the two and starts the sweeps from its answer.
+// 1 runs BiCGStab between the two and starts the sweeps from its answer.  A
+// field on scheme 1 takes its right-hand side from the gradient pass and the
+// limited assembly instead; everything after the assembly is the same.
 #include <cmath>
 #include <cstring>
 
@@ -29,6 +31,8 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   sc_partial = nullptr;
   for (float*& v : kr_vec) v = nullptr;
   kr_partial = kr_state = nullptr;
+  hr_grad = nullptr;
+  hr_count = nullptr;
   for (ScalarField& f : sc_field) f = ScalarField{};
   if (count == 0) return;
   const size_t ld = topo.ld;
@@ -102,8 +106,28 @@ void Solver::scalar_advance(float dt) {
     A.coef = sc_coef;
     A.diag = sc_diag;
     A.b = sc_b;
-    launch_scalar_assemble(A, stream);
-    check_launch("scalar assemble");
+    f.scheme_used = f.scheme;
+    f.clamped = 0;
+    if (f.scheme == 1) {
+      // the gradient of phi_old first, every cell before any is read; then the
+      // assembly with the limited right-hand side.  The count lands in
+      // f.clamped with the first read of the solve below.
+      ScalarGradArgs G{};
+      G.N = N;
+      G.fs = fs;
+      G.vol = d_vol;
+      G.phi_old = f.phi;
+      G.inlet_value = f.par.inlet_value;
+      G.g = hr_grad;
+      launch_scalar_grad(G, stream);
+      CFD_HIP(hipMemsetAsync(hr_count + fi, 0, sizeof(uint32_t), stream));
+      launch_scalar_assemble_limited(ScalarLimitedArgs{A, hr_grad, hr_count + fi}, stream);
+      check_launch("scalar limited assemble");
+      CFD_HIP(hipMemcpyAsync(&f.clamped, hr_count + fi, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    } else {
+      launch_scalar_assemble(A, stream);
+      check_launch("scalar assemble");
+    }
     f.sweeps = 0;
     f.converged = 0;
     f.dt_used = dt;
@@ -215,6 +239,29 @@ void Solver::set_scalar_solver(int field, const cfd_scalar_solver& c) {
   }
   sc_field[field].solver = c;
   sc_field[field].solver.reserved = 0;
+}
+
+void Solver::set_scalar_scheme(int field, const cfd_scalar_scheme& c) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar scheme on a distributed handle");
+  scalar_check(field);
+  if (c.scheme != 0 && c.scheme != 1)
+    throw std::invalid_argument("scalar scheme: scheme must be 0 (upwind) or 1 (limited linear)");
+  if (c.scheme == 1 && !hr_grad) {
+    if (topo.wf > 32) throw std::invalid_argument("scalar scheme 1 keeps a cell's inlet slots in 32 bits: more than 32 faces per cell");
+    CFD_HIP(hipSetDevice(device));
+    hr_grad = sc_arena.alloc<float2>(topo.ld);
+    hr_count = sc_arena.alloc<uint32_t>(4);
+    CFD_HIP(hipMemsetAsync(hr_count, 0, 4 * sizeof(uint32_t), stream));
+  }
+  sc_field[field].scheme = c.scheme;
+}
+
+void Solver::scalar_scheme_stats(int field, cfd_scalar_scheme_stats* out) const {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar scheme on a distributed handle");
+  scalar_check(field);
+  std::memset(out, 0, sizeof(*out));
+  out->scheme = sc_field[field].scheme_used;
+  out->clamped_cells = sc_field[field].clamped;
 }
 
 void Solver::scalar_stats(int field, cfd_scalar_stats* out) {

@@ -596,6 +596,9 @@ struct Solver {
     float dt_used = 0.0f;
     cfd_scalar_solver solver{0, 500, 8, 0};  // cfd_scalar_solver_default
     cfd_scalar_solver_stats kstats{};        // of the last advance
+    int32_t scheme = 0;                      // cfd_scalar_scheme.scheme, for the next advance
+    int32_t scheme_used = 0;                 // of the last advance
+    uint32_t clamped = 0;                    // of the last advance (copied from hr_count during it)
   };
   DeviceArena sc_arena;
   int sc_count = 0;
@@ -613,6 +616,10 @@ struct Solver {
   float* kr_vec[6] = {};           // [ld] each: rh, r, p, v, s, t
   double* kr_partial = nullptr;    // [2 * pstride] unit partials of an iteration's dots
   double* kr_state = nullptr;      // [0..3] rho, alpha, omega (f64); then 8 status words; then alpha, omega, beta (f32)
+  // Scheme 1 (limited linear) work space, allocated in sc_arena by the first
+  // set_scalar_scheme that selects it (null before)
+  float2* hr_grad = nullptr;       // [ld] the gradient of the phi_old being advanced
+  uint32_t* hr_count = nullptr;    // [4] clamped cells of each field's last scheme-1 assembly
   float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
   void scalars_enable(int count, const cfd_scalar_config& c);
   void scalar_check(int field) const;  // throws std::invalid_argument: not enabled / bad index
@@ -620,6 +627,8 @@ struct Solver {
   void get_scalar(int field, double* phi);
   void scalar_advance(float dt);
   void set_scalar_solver(int field, const cfd_scalar_solver& c);
+  void set_scalar_scheme(int field, const cfd_scalar_scheme& c);
+  void scalar_scheme_stats(int field, cfd_scalar_scheme_stats* out) const;
   void scalar_krylov(ScalarField& f);   // the Krylov phase of one assembled field: f.phi becomes its frozen x
   void scalar_polish(int fi, ScalarField& f);   // the Jacobi loop from f.phi: sweeps, last_delta, converged
   void scalar_stats(int field, cfd_scalar_stats* out);

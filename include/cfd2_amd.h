@@ -670,6 +670,78 @@ void cfd_scalar_solver_default(cfd_scalar_solver* cfg); /* method 0, 500, 8 */
 cfd_status cfd_set_scalar_solver(cfd_solver* s, int32_t field, const cfd_scalar_solver* cfg);
 cfd_status cfd_scalar_solver_stats_get(cfd_solver* s, int32_t field, cfd_scalar_solver_stats* out);
 
+/* Advection scheme of one scalar field.  Scheme 0 (the default) is the bounded
+ * first-order upwind system above, unchanged.  Scheme 1, "limited linear", adds
+ * a van Leer-limited linear-upwind face value as a deferred correction,
+ * evaluated once per advance on phi_old and clamped so that the maximum
+ * principle of scheme 0 still holds: coef (c_k) and diag are exactly scheme
+ * 0's, only b changes, and the Jacobi loop, method 1 and the statistics run
+ * unchanged on it.  A handle that never selects scheme 1 allocates and
+ * launches nothing new, and cfd_step launches none of it in any case; the
+ * first selection allocates one gradient (two f32 per cell) and a counter word
+ * per field, freed by cfd_scalars_enable(0).
+ *
+ * Arithmetic of scheme 1.  All f32, one rounding per operation (nothing
+ * fused), every sum left to right in face-slot order.  phi = phi_old; phi_i the
+ * cell's own value, phi_o = phi[o_k] the neighbour's of internal slot k; F_k
+ * the mass flux out of cell i through slot k; n_k = (nx, ny)_k the unit normal
+ * out of cell i; A_k the area; lam_k the cell-side interpolation weight the
+ * step's own gradients use, and "degenerate" its fallback flag (the two
+ * centre-to-face distances add up to <= 1e-6); dv_k = (dvx, dvy)_k = the
+ * neighbour's centre minus the cell's.
+ *   gradient   face value vf_k:
+ *                internal            lam_k * phi_i + (1 - lam_k) * phi_o
+ *                internal, degenerate  0.5 * (phi_i + phi_o)
+ *                inlet               inlet_value
+ *                wall, outlet        phi_i
+ *              gx = sum_k (vf_k * nx_k) * A_k, gy = sum_k (vf_k * ny_k) * A_k
+ *              over every used slot, each from +0;  g_i = (gx / vol_i, gy /
+ *              vol_i), true divisions.  Every g is formed before any is used.
+ *   increment  per internal slot, h_k:
+ *                F_k > 0 (cell i is upwind)    d = phi_o - phi_i
+ *                                              gd = g_i.x * dvx_k + g_i.y * dvy_k
+ *                F_k < 0 (the neighbour is)    d = phi_i - phi_o
+ *                                              gd = -(g_o.x * dvx_k + g_o.y * dvy_k)
+ *                otherwise (F_k == 0)          the slot is skipped
+ *              d == 0: h_k = 0.  Otherwise r = (2 * gd) / d - 1;
+ *              psi = r > 0 ? 2 / (1 + 1 / r) : 0;  h_k = (0.5 * psi) * d.
+ *              (psi is van Leer's (r + |r|) / (1 + |r|) of the ratio r of the
+ *              upwind-side to the face difference, written so that r = +inf
+ *              gives 2 and a denormal r gives 0; the face value is the upwind
+ *              cell's plus h_k.)  corr_i = sum_k F_k * h_k over those slots,
+ *              from +0.  Boundary slots carry no correction: the inlet stays
+ *              first-order.
+ *   clamp      m_i, M_i start as phi_i and take, in slot order, v < m ? v : m
+ *              and v > M ? v : M with v = phi_o on internal slots and v =
+ *              inlet_value on inlet slots.
+ *                t  = a_t * phi_i - corr_i;  lo = a_t * m_i;  hi = a_t * M_i
+ *                t  = t < lo ? lo : (t > hi ? hi : t)
+ *              (comparisons: a NaN t stays NaN and the advance returns
+ *              CFD_ERR_DIVERGED as before).  b_i = t, then + c_k * inlet_value
+ *              per inlet slot in slot order.  A cell counts as clamped when
+ *              t < lo or t > hi held.
+ * The bound: with v_i = b's t / a_t inside the range of phi_old over the cell,
+ * its neighbours and the inlet, every Jacobi iterate (a_t v_i + sum_k c_k
+ * phi_j + inlet terms) / diag_i is a convex combination with scheme 0's
+ * weights of values inside that range, converged or not, so a dye in [0, 1]
+ * stays there up to the same rounding as under scheme 0 (method 1 keeps its
+ * own, wider bound).  The correction is not repeated: one pass per advance.  */
+typedef struct cfd_scalar_scheme {
+  int32_t scheme;          /* 0 upwind, 1 limited linear (van Leer) */
+  int32_t reserved[3];
+} cfd_scalar_scheme;
+typedef struct cfd_scalar_scheme_stats {
+  int32_t scheme;          /* of the last cfd_scalar_advance, this field */
+  uint32_t clamped_cells;  /* cells whose t the clamp changed in it; 0 under scheme 0 */
+  int32_t reserved[2];
+} cfd_scalar_scheme_stats;
+void cfd_scalar_scheme_default(cfd_scalar_scheme* cfg); /* scheme 0; null ignored */
+/* Takes effect at the next cfd_scalar_advance.  CFD_ERR_INVALID: scalars not
+ * enabled, a bad field index, a scheme other than 0 or 1, a distributed
+ * handle.  cfd_scalars_enable resets every field to scheme 0.               */
+cfd_status cfd_set_scalar_scheme(cfd_solver* s, int32_t field, const cfd_scalar_scheme* cfg);
+cfd_status cfd_scalar_scheme_stats_get(cfd_solver* s, int32_t field, cfd_scalar_scheme_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

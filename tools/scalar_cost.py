@@ -23,6 +23,14 @@ fenced calls each (Jacobi with max_sweeps raised until it converges); the time
 of one BiCGStab iteration as (128 iterations - 64 iterations) / 64 at tol = 0,
 its layout bytes over that time, and the sweep kernel's rate as in (b).
 Writes profiles/r09/scalar_krylov.json.
+
+--scheme: instead, the extra time of a scheme-1 ("limited linear", van Leer)
+advance over a scheme-0 advance (set_scalar_scheme) on one handle in one
+session: one field at dt = 1e-3, D = 1e-4, every advance from the same step
+profile and exactly 4 sweeps long, medians of 20 fenced calls, scheme 0 timed
+before and after scheme 1; beside it the layout bytes of the two new passes
+less those of the assembly they replace, at the sweep kernel's rate of the
+same session.  Writes profiles/r10/scalar_hr.json.
 """
 from __future__ import annotations
 
@@ -105,6 +113,59 @@ def krylov_rows(s, mesh, name, np):
     return rows, rate
 
 
+def scheme_layout_bytes(mesh) -> dict:
+    """Layout bytes, each element of a pass once.  k_scalar_assemble: per used
+    slot other, meta, flux_s, area, dist_e and the coef written (24 B); per cell
+    nface, vol, phi_old, diag, b (20 B).  k_scalar_grad: per used slot other,
+    meta, area, nx, ny, lam_s (24 B); per cell nface, vol, the phi_old gathers
+    counted once, the 8-byte g written (20 B).  k_scalar_assemble_limited: the
+    assembly's slot streams plus dvx, dvy (32 B); per cell the assembly's 20 B
+    and the g gathers counted once (28 B)."""
+    slots, n = float(mesh.arrays()["cell_face_offsets"][-1]), float(mesh.num_cells())
+    return dict(assemble=24.0 * slots + 20.0 * n, grad=24.0 * slots + 20.0 * n, limited=32.0 * slots + 28.0 * n)
+
+
+def scheme_row(s, mesh, name, np):
+    """One advance under scheme 0 and under scheme 1 on one handle: every call
+    starts from the same step profile and runs exactly one batch of 4 sweeps
+    (max_sweeps = check_interval = 4), so the two differ by the assembly alone;
+    medians of 20 fenced calls, scheme 0 timed before and after scheme 1."""
+    x = mesh.arrays()["cell_cx"]
+    dye = np.where(x < 0.5, 1.0, 0.0)
+
+    def run(scheme, reps=20, **cfg):
+        s.enable_scalars(1, **cfg)
+        s.set_scalar_params(0, DIFFUSIVITY, 1.0)
+        s.set_scalar_scheme(0, scheme)
+        ts = []
+        for _ in range(reps + 1):  # the first call is the warm-up
+            s.set_scalar(0, dye)
+            s.synchronize()
+            t0 = time.perf_counter()
+            s.advance_scalars()
+            s.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts[1:]), min(ts[1:]), s.scalar_scheme_stats(0)
+
+    one = dict(max_sweeps=4, check_interval=4)
+    u0, u0_min, _ = run("upwind", **one)
+    v, v_min, hs = run("vanleer", **one)
+    u1, u1_min, _ = run("upwind", **one)
+    t64, _, _ = run("upwind", reps=10, max_sweeps=64, check_interval=64)
+    sweep = (t64 - 0.5 * (u0 + u1)) / 60.0  # 60 more sweeps, the same assembly and one read
+    lb, sb = scheme_layout_bytes(mesh), sweep_layout_bytes(mesh)
+    extra = v - 0.5 * (u0 + u1)
+    extra_bytes = lb["grad"] + lb["limited"] - lb["assemble"]
+    rate = sb / sweep
+    return dict(config=name, cells=mesh.num_cells(), dt=1e-3, diffusivity=DIFFUSIVITY, sweeps_per_call=4,
+                upwind_ms=1e3 * u0, upwind_min_ms=1e3 * u0_min, vanleer_ms=1e3 * v, vanleer_min_ms=1e3 * v_min,
+                upwind_again_ms=1e3 * u1, upwind_again_min_ms=1e3 * u1_min, clamped_cells=int(hs.clamped_cells),
+                extra_us=1e6 * extra, extra_layout_bytes=extra_bytes, extra_gbs=extra_bytes / extra / 1e9,
+                sweep_us=1e6 * sweep, sweep_layout_bytes=sb, sweep_gbs=rate / 1e9,
+                extra_at_sweep_rate_us=1e6 * extra_bytes / rate, extra_in_sweeps=extra / sweep,
+                layout_bytes=lb)
+
+
 def fenced(solver, fn, reps=20):
     ts, sweeps = [], []
     for _ in range(reps):
@@ -123,9 +184,13 @@ def main():
     ap.add_argument("--mesh-cache-dir", default=None, help="load / save <dir>/<config>.mesh (bench.py --mesh-cache files)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--krylov", action="store_true", help="Jacobi against BiCGStab (profiles/r09/scalar_krylov.json)")
+    ap.add_argument("--scheme", action="store_true", help="scheme 1 against scheme 0 (profiles/r10/scalar_hr.json)")
     args = ap.parse_args()
+    if args.krylov and args.scheme:
+        ap.error("--krylov and --scheme are separate runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", *(("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")))
+        where = ("r10", "scalar_hr.json") if args.scheme else ("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")
+        args.out = os.path.join(ROOT, "profiles", *where)
     import numpy as np
     from cfd2_amd import GpuSolver, build_id, default_config
     from cfd2_amd.mesh import Mesh, bench_channel
@@ -147,6 +212,16 @@ def main():
         s.set_alpha_p(0.3)
         s.set_precond_type(1)
         s.initialize_history()
+        if args.scheme:
+            s.step()
+            s.step()
+            row = scheme_row(s, mesh, name, np)
+            row["build"] = build_id()
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            s.close()
+            del mesh
+            continue
         if args.krylov:
             s.step()
             s.step()
@@ -194,6 +269,16 @@ def main():
         s.close()
         del mesh
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.scheme:
+        with open(args.out, "w") as fh:
+            json.dump(dict(what="one field, dt 1e-3, D 1e-4, one handle after 2 steps, every advance from the same step "
+                                "profile and one batch of 4 sweeps long (tools/scalar_cost.py --scheme): medians of 20 "
+                                "fenced advance_scalars() calls under scheme 0, scheme 1 and scheme 0 again; extra = "
+                                "scheme 1 - the mean of the two scheme-0 medians; one sweep = (64 sweeps - 4 sweeps) / 60; "
+                                "layout bytes with each element of a pass once",
+                           rows=rows), fh, indent=1)
+            fh.write("\n")
+        return
     if args.krylov:
         with open(args.out, "w") as fh:
             json.dump(dict(what="one field, dt 1e-3, one handle after 2 steps, every advance from the same step profile "
