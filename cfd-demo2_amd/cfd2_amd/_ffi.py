@@ -214,6 +214,45 @@ class ScalarSchemeStats(C.Structure):  # cfd_scalar_scheme_stats
         return {"scheme": self.scheme, "clamped_cells": self.clamped_cells}
 
 
+class AmgLevel(C.Structure):  # cfd_amg_level
+    _fields_ = [
+        ("n", C.c_uint32), ("nc", C.c_uint32), ("nnz", C.c_uint64), ("r_nnz", C.c_uint64),
+        ("wide", C.c_int32), ("use16", C.c_int32),
+        ("row", C.POINTER(C.c_uint32)), ("col", C.POINTER(C.c_uint32)), ("val", C.POINTER(C.c_float)),
+        ("dv", C.POINTER(C.c_float)), ("de", C.POINTER(C.c_float)),
+        ("agg", C.POINTER(C.c_uint32)), ("r_row", C.POINTER(C.c_uint32)), ("r_col", C.POINTER(C.c_uint32)),
+        ("m4", C.POINTER(C.c_int32)), ("m4_more", C.POINTER(C.c_int32)),
+    ]
+
+
+def amg_level_readback(call) -> dict:
+    """The two-call read-back of one AMG level (cfd_debug_amg_level and the
+    oracle's mirror): ``call(ptr)`` runs the entry on a cfd_amg_level.  Returns
+    plain numpy arrays; agg / r_row / r_col / m4 / m4_more are None on a level
+    without a coarse level."""
+    import numpy as np
+    lv = AmgLevel()
+    call(C.byref(lv))
+    n, nc, nnz, rn = int(lv.n), int(lv.nc), int(lv.nnz), int(lv.r_nnz)
+    out = dict(n=n, nc=nc, nnz=nnz, wide=bool(lv.wide), use16=bool(lv.use16),
+               row=np.zeros(n + 1, np.uint32), col=np.zeros(nnz, np.uint32), val=np.zeros(nnz, np.float32),
+               dv=np.zeros(n, np.float32), de=np.zeros(n, np.float32),
+               agg=None, r_row=None, r_col=None, m4=None, m4_more=None)
+    if nc:
+        out.update(agg=np.zeros(n, np.uint32), r_row=np.zeros(nc + 1, np.uint32), r_col=np.zeros(rn, np.uint32),
+                   m4=np.zeros(4 * nc, np.int32), m4_more=np.zeros(nc, np.int32))
+    for name, ctype in (("row", C.c_uint32), ("col", C.c_uint32), ("val", C.c_float), ("dv", C.c_float),
+                        ("de", C.c_float), ("agg", C.c_uint32), ("r_row", C.c_uint32), ("r_col", C.c_uint32),
+                        ("m4", C.c_int32), ("m4_more", C.c_int32)):
+        if out[name] is not None:
+            setattr(lv, name, out[name].ctypes.data_as(C.POINTER(ctype)))
+    call(C.byref(lv))
+    assert (int(lv.n), int(lv.nc), int(lv.nnz), int(lv.r_nnz)) == (n, nc, nnz, rn)
+    if nc:
+        out["m4"] = out["m4"].reshape(nc, 4)
+    return out
+
+
 class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     _fields_ = [
         ("magic", C.c_char * 8),
@@ -272,7 +311,8 @@ EXPORTED = [
     "cfd_group_state_save", "cfd_profile_enable", "cfd_profile_reset",
     "cfd_profile_smoother", "cfd_graph_enable", "cfd_graph_stats", "cfd_amg_levels", "cfd_step_algorithmic_bytes", "cfd_smoother_layout_bytes", "cfd_step_layout_bytes", "cfd_debug_buffer",
     "cfd_debug_buffer_len", "cfd_debug_prepare_assemble", "cfd_debug_reference_semantics", "cfd_debug_amg_info",
-    "cfd_debug_column_widths",
+    "cfd_debug_column_widths", "cfd_debug_amg_level", "cfd_debug_amg_vcycle",
+    "cfd_debug_apply_precond",
     "cfd_dist_unique_id", "cfd_solver_create_dist", "cfd_solver_create_dist_host", "cfd_group_create",
     "cfd_group_step",
     "cfd_dist_info", "cfd_dist_plan", "cfd_debug_rccl_selftest", "cfd_debug_comm_watchdog", "cfd_dist_comm_stats",

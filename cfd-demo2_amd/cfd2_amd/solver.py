@@ -72,6 +72,10 @@ def _bind():
     L.cfd_debug_reference_semantics.argtypes = [_vp, C.c_int32]
     L.cfd_debug_amg_info.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     L.cfd_debug_column_widths.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.cfd_debug_amg_level.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.AmgLevel)]
+    L.cfd_debug_apply_precond.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+    L.cfd_debug_amg_vcycle.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.c_size_t]
     u8p = C.POINTER(C.c_uint8)
     u32p = C.POINTER(C.c_uint32)
     L.cfd_dist_unique_id.argtypes = [u8p]
@@ -529,6 +533,34 @@ class GpuSolver:
 
     def debug_prepare_assemble(self, assemble=True):
         self._call("cfd_debug_prepare_assemble", 1 if assemble else 0)
+
+    def debug_apply_precond(self, v) -> np.ndarray:
+        """z = M^-1 v, one application of the FGMRES preconditioner outside the
+        solve (cfd_debug_apply_precond); v, z: 3 num_cells floats, (u, v, p) per cell."""
+        v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        assert v.size == 3 * self.num_cells
+        z = np.zeros(v.size, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self._call("cfd_debug_apply_precond", v.ctypes.data_as(fp), z.ctypes.data_as(fp), v.size)
+        return z
+
+    def debug_amg_level(self, level: int) -> dict:
+        """Level ``level`` of the built hierarchy as plain CSR with its diagonals
+        and transfer operators, expanded from the device image
+        (cfd_debug_amg_level; _ffi.amg_level_readback for the keys)."""
+        return _ffi.amg_level_readback(lambda p: self._call("cfd_debug_amg_level", int(level), p))
+
+    def debug_amg_vcycle(self, x0, b) -> np.ndarray:
+        """One V-cycle of the preconditioner on (x0, b), outside the solve
+        (cfd_debug_amg_vcycle); f32 in, f32 out."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        assert x0.shape == b.shape == (self.num_cells,)
+        out = np.zeros(self.num_cells, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self._call("cfd_debug_amg_vcycle", x0.ctypes.data_as(fp), b.ctypes.data_as(fp), out.ctypes.data_as(fp),
+                   self.num_cells)
+        return out
 
     def debug_reference_semantics(self, flags):
         """Test mode: the reference's own semantics (oracle flag bits 1 / 4 /

@@ -149,17 +149,23 @@ bool Solver::level_csr(const AmgLevelDev& d, std::vector<uint32_t>& row, std::ve
   auto d2h = [&](void* dst, const void* src, size_t bytes) {
     if (bytes) CFD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
   };
-  std::vector<uint8_t> len(n);
+  std::vector<uint8_t> len8(d.len16 ? 0 : n);
+  std::vector<uint16_t> len(n);  // a wide level keeps its true lengths in len16 (len holds min(., 255))
   std::vector<float> v(val ? slots : 0);
   std::vector<int16_t> c16(d.use16 ? slots : 0);
   std::vector<int32_t> c32(d.use16 ? 0 : slots);
-  d2h(len.data(), d.len, n);
+  if (d.len16) d2h(len.data(), d.len16, (size_t)n * 2);
+  else d2h(len8.data(), d.len, n);
   if (val) d2h(v.data(), d.val, slots * 4);
   if (d.use16) d2h(c16.data(), d.col16, slots * 2);
   else d2h(c32.data(), d.col32, slots * 4);
   sync();
+  if (!d.len16) std::copy(len8.begin(), len8.end(), len.begin());
   row.assign((size_t)n + 1, 0);
-  for (uint32_t i = 0; i < n; ++i) row[i + 1] = row[i] + len[i];
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((int)len[i] > d.w) throw std::logic_error("AMG level image: a row longer than the level's width");
+    row[i + 1] = row[i] + len[i];
+  }
   col.resize(row[n]);
   if (val) val->resize(row[n]);
   for (uint32_t i = 0; i < n; ++i)

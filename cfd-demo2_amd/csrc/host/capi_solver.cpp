@@ -304,6 +304,19 @@ cfd_status cfd_debug_buffer(cfd_solver* s, int32_t id, float* out, size_t count)
   if (!out || len == 0 || count < len) return set_error(CFD_ERR_INVALID, "bad debug buffer request");
   return guard([&] { s->s->debug_buffer(id, out); });
 }
+cfd_status cfd_debug_amg_level(cfd_solver* s, int32_t level, cfd_amg_level* io) {
+  CHECK_S(s);
+  if (!io) return set_error(CFD_ERR_INVALID, "null level");
+  return guard([&] { s->s->debug_amg_level(level, io); });
+}
+cfd_status cfd_debug_amg_vcycle(cfd_solver* s, const float* x0, const float* b, float* x_out, size_t n) {
+  CHECK_S(s);
+  return guard([&] { s->s->debug_amg_vcycle(x0, b, x_out, n); });
+}
+cfd_status cfd_debug_apply_precond(cfd_solver* s, const float* v, float* z, size_t n3) {
+  CHECK_S(s);
+  return guard([&] { s->s->debug_apply_precond(v, z, n3); });
+}
 cfd_status cfd_debug_prepare_assemble(cfd_solver* s, int32_t assemble) {
   CHECK_S(s);
   return guard([&] { s->s->debug_prepare_assemble(assemble != 0); });

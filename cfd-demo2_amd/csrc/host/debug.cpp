@@ -1,6 +1,7 @@
 // Test-only entry points: the reference-semantics mode (the reference's own
 // reduction orders, racy prepare and in-place smoother under a legal schedule,
-// cfd_debug_reference_semantics) and the read-backs of cfd_debug_buffer.
+// cfd_debug_reference_semantics), the read-backs of cfd_debug_buffer and of
+// the AMG levels, and the V-cycle / preconditioner applied outside the solve.
 #include <algorithm>
 
 #include "solver_impl.hpp"
@@ -91,6 +92,119 @@ void Solver::debug_prepare_assemble(bool asmb) {
   constants.component = 0;
   prepare();
   if (asmb) assemble();
+  sync();
+}
+
+// One level as plain CSR from the arrays the V-cycle kernels read: the
+// off-diagonal slots (level_csr: u8 or, on a wide level, u16 lengths; 16-bit
+// deltas or 32-bit columns), the diagonal put back at its rank with the value
+// dv, then dv / de and the transfer operators.  Sizes first; arrays when the
+// caller passes them.
+void Solver::debug_amg_level(int li, cfd_amg_level* io) {
+  if (dist()) throw std::invalid_argument("AMG level read-back: one GPU only");
+  if (!amg_built) throw std::invalid_argument("AMG level read-back: no hierarchy built yet");
+  if (li < 0 || li >= (int)levels.size()) throw std::invalid_argument("no such AMG level");
+  CFD_HIP(hipSetDevice(device));
+  const AmgGpuLevel& G = levels[li];
+  const AmgLevelDev& d = G.dev;
+  const uint32_t n = d.n, nc = d.nc;
+  auto d2h = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes) CFD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+  };
+  std::vector<uint32_t> r_row((size_t)(nc ? nc + 1 : 0));
+  d2h(r_row.data(), d.r_row, r_row.size() * 4);
+  sync();
+  const size_t r_nnz = nc ? r_row[nc] : 0;
+  const bool fill = io->row || io->col || io->val || io->dv || io->de || io->agg || io->r_row || io->r_col ||
+                    io->m4 || io->m4_more;
+  if (fill && (io->n != n || io->nc != nc || io->nnz != G.nnz || io->r_nnz != r_nnz))
+    throw std::invalid_argument("AMG level read-back: the sizes are not those of the first call");
+  io->n = n;
+  io->nc = nc;
+  io->nnz = G.nnz;
+  io->r_nnz = r_nnz;
+  io->wide = d.len16 ? 1 : 0;  // what the kernels read
+  io->use16 = d.use16;
+  if (!fill) return;
+  // ---- the matrix ----
+  std::vector<uint8_t> dr8(d.drank16 ? 0 : n);
+  std::vector<uint16_t> dr(n);
+  std::vector<float> dv(n), de(n);
+  if (d.drank16) d2h(dr.data(), d.drank16, (size_t)n * 2);
+  else d2h(dr8.data(), d.drank, n);
+  d2h(dv.data(), d.dv, (size_t)n * 4);
+  d2h(de.data(), d.de, (size_t)n * 4);
+  std::vector<uint32_t> orow, ocol;
+  std::vector<float> oval;
+  if (!level_csr(d, orow, ocol, &oval)) throw std::logic_error("AMG level read-back: a column outside the level");
+  if (!d.drank16) std::copy(dr8.begin(), dr8.end(), dr.begin());
+  if ((uint64_t)orow[n] + n != G.nnz)
+    throw std::logic_error("AMG level read-back: the image's row lengths do not add up to the level's nnz");
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t o0 = orow[i], len = orow[i + 1] - o0;
+    if (dr[i] > len) throw std::logic_error("AMG level read-back: a diagonal rank past its row");
+    const size_t k0 = (size_t)o0 + i;  // i diagonals precede row i
+    if (io->row) io->row[i] = (uint32_t)k0;
+    for (uint32_t r = 0; r <= len; ++r) {
+      const bool diag = r == dr[i];
+      const uint32_t src = o0 + (r > dr[i] ? r - 1 : r);
+      if (io->col) io->col[k0 + r] = diag ? i : ocol[src];
+      if (io->val) io->val[k0 + r] = diag ? dv[i] : oval[src];
+    }
+  }
+  if (io->row) io->row[n] = (uint32_t)G.nnz;
+  if (io->dv) std::copy(dv.begin(), dv.end(), io->dv);
+  if (io->de) std::copy(de.begin(), de.end(), io->de);
+  if (!nc) return;
+  // ---- P, R and the 4-member image of R ----
+  std::vector<int32_t> m4(4 * (size_t)nc);
+  if (io->agg) d2h(io->agg, d.agg, (size_t)n * 4);
+  if (io->r_col) d2h(io->r_col, d.r_col, r_nnz * 4);
+  d2h(m4.data(), d.r_m4, m4.size() * 4);
+  sync();
+  if (io->r_row) std::copy(r_row.begin(), r_row.end(), io->r_row);
+  for (uint32_t I = 0; I < nc; ++I) {
+    const int32_t w = m4[4 * (size_t)I + 3];  // < -1: more than four members, member 3 = -2 - w
+    for (int q = 0; q < 4 && io->m4; ++q) io->m4[4 * (size_t)I + q] = (q == 3 && w < -1) ? -2 - w : m4[4 * (size_t)I + q];
+    if (io->m4_more) io->m4_more[I] = w < -1 ? 1 : 0;
+  }
+}
+
+// apply_precond's cycle on caller-given vectors: eager launches on the solver's
+// stream (no graph is being captured between steps), level 0 bound to
+// (p_sol, temp_p) as every cycle binds it.  Both vectors are rewritten by the
+// next Schur prediction before anything reads them.
+void Solver::debug_amg_vcycle(const float* x0, const float* b, float* out, size_t n) {
+  if (dist()) throw std::invalid_argument("AMG V-cycle call: one GPU only");
+  if (!amg_built || !fgmres_ready) throw std::invalid_argument("AMG V-cycle call: no hierarchy built yet");
+  if (n != N || !x0 || !b || !out) throw std::invalid_argument("AMG V-cycle call: vectors of num_cells floats");
+  if (capturing) throw std::logic_error("AMG V-cycle call inside a graph capture");
+  CFD_HIP(hipSetDevice(device));
+  CFD_HIP(hipMemcpyAsync(p_sol, x0, (size_t)N * 4, hipMemcpyHostToDevice, stream));
+  CFD_HIP(hipMemcpyAsync(temp_p, b, (size_t)N * 4, hipMemcpyHostToDevice, stream));
+  v_cycle();
+  check_launch("AMG V-cycle (debug call)");
+  CFD_HIP(hipMemcpyAsync(out, p_sol, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+  sync();
+}
+
+// precondition(0, Z_0) on a caller-given V_0 (binv[0] = 1: V_0 is read as it
+// is).  Basis slot 0, binv[0], Z slot 0 and the pressure scratch are written
+// by every solve's start and first iteration before they are read.
+void Solver::debug_apply_precond(const float* v, float* z, size_t n3) {
+  if (dist()) throw std::invalid_argument("preconditioner call: one GPU only");
+  if (!fgmres_ready) throw std::invalid_argument("preconditioner call: no step solved yet");
+  if (constants.precond_type == 1 && !amg_built)
+    throw std::invalid_argument("preconditioner call: no hierarchy built yet");
+  if (n3 != 3 * (size_t)N || !v || !z) throw std::invalid_argument("preconditioner call: vectors of 3 num_cells floats");
+  if (capturing) throw std::logic_error("preconditioner call inside a graph capture");
+  CFD_HIP(hipSetDevice(device));
+  const float one = 1.0f;
+  CFD_HIP(hipMemcpyAsync(basis, v, n3 * 4, hipMemcpyHostToDevice, stream));
+  CFD_HIP(hipMemcpyAsync(binv, &one, 4, hipMemcpyHostToDevice, stream));
+  precondition(0, zvec);
+  check_launch("preconditioner (debug call)");
+  CFD_HIP(hipMemcpyAsync(z, zvec, n3 * 4, hipMemcpyDeviceToHost, stream));
   sync();
 }
 

@@ -552,6 +552,9 @@ struct Solver {
   void debug_prepare_assemble(bool assemble);
   size_t debug_len(int id) const;
   void debug_buffer(int id, float* out);
+  void debug_amg_level(int li, cfd_amg_level* io);  // sizes, then arrays (cfd_debug_amg_level)
+  void debug_amg_vcycle(const float* x0, const float* b, float* out, size_t n);
+  void debug_apply_precond(const float* v, float* z, size_t n3);  // z = M^-1 v through precondition(0, .)
   // ---- accounting.cpp: the byte models ----
   double algorithmic_step_bytes() const;
   double layout_step_bytes() const;
@@ -846,7 +849,8 @@ struct Solver {
   void build_tail_blob(int tf, bool reuse = false);  // reuse: rewrite the existing blob in place
   void set_resrestrict_blocks();
   // A level's off-diagonal pattern as CSR in slot order, decoded from its ELL
-  // image (16-bit deltas included); val: the entries' values too.  One sync(),
+  // image (16-bit deltas and a wide level's 16-bit lengths included); val: the
+  // entries' values too.  One sync(),
   // which also completes the downloads the caller queued before the call.
   // False when a column lies outside the level's rows (a row-partitioned level).
   bool level_csr(const AmgLevelDev& d, std::vector<uint32_t>& row, std::vector<uint32_t>& col,

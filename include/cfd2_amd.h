@@ -324,6 +324,54 @@ cfd_status cfd_debug_amg_info(cfd_solver* s, int32_t level, int32_t* setup_path,
  * only: allocates nothing, launches nothing.  Debug/parity only.            */
 cfd_status cfd_debug_column_widths(const cfd_solver* s, int32_t* coupled_use16, int32_t* num_levels,
                                    int32_t* level_use16 /*[20]*/);
+/* One level of the built AMG hierarchy as plain CSR, expanded from the device
+ * image the V-cycle kernels read (ELL values, 16/32-bit columns, u8 / u16 row
+ * lengths and diagonal ranks, dv, de, agg, R, r_m4), never from a host copy
+ * kept by the setup.  Two calls: with every pointer NULL the call fills the
+ * sizes (n, nnz, nc, r_nnz, wide, use16); with the arrays allocated to those
+ * sizes it fills them (a NULL array is skipped).  row/col/val: columns
+ * ascending, the diagonal included (value dv); agg, r_row, r_col, m4, m4_more
+ * only when nc > 0 (the level has a coarse level).  m4[4 I + q]: member q of
+ * aggregate I as the r_m4 image lists it (-1: none); m4_more[I]: 1 when the
+ * image flags more than four members.  Debug/parity only; one GPU only (a
+ * distributed handle, no hierarchy, or no such level: CFD_ERR_INVALID).     */
+typedef struct cfd_amg_level {
+  uint32_t n;       /* rows                                                  */
+  uint32_t nc;      /* aggregates (rows of the next level); 0: last level    */
+  uint64_t nnz;     /* entries of row/col/val, diagonal included             */
+  uint64_t r_nnz;   /* entries of r_col (= n when every row has an aggregate) */
+  int32_t wide;     /* 1: 16-bit row lengths (tail kernels only)             */
+  int32_t use16;    /* 1: 16-bit column deltas                               */
+  uint32_t* row;    /* [n + 1]                                               */
+  uint32_t* col;    /* [nnz]                                                 */
+  float* val;       /* [nnz]                                                 */
+  float* dv;        /* [n] raw diagonal                                      */
+  float* de;        /* [n] smoother diagonal                                 */
+  uint32_t* agg;    /* [n]                                                   */
+  uint32_t* r_row;  /* [nc + 1]                                              */
+  uint32_t* r_col;  /* [r_nnz]                                               */
+  int32_t* m4;      /* [4 nc]                                                */
+  int32_t* m4_more; /* [nc]                                                  */
+} cfd_amg_level;
+cfd_status cfd_debug_amg_level(cfd_solver* s, int32_t level, cfd_amg_level* io);
+/* One application of the AMG V-cycle outside the solve: uploads x0 to the
+ * level-0 solution vector and b to its right-hand side, runs exactly the cycle
+ * the preconditioner runs (the planned schedule under the knobs in force; the
+ * plain cycle when reference semantics 1 / 8 are on), synchronises and returns
+ * the solution vector.  Never inside a captured graph; touches only those two
+ * vectors and the level scratch, so a later step gives the bits of a solver
+ * that never called it.  n must be cfd_num_cells.  Needs a built hierarchy;
+ * debug/parity only; one GPU only (else CFD_ERR_INVALID).                    */
+cfd_status cfd_debug_amg_vcycle(cfd_solver* s, const float* x0, const float* b, float* x_out, size_t n);
+/* One application of the FGMRES preconditioner outside the solve: z = M^-1 v
+ * for v, z of 3 cfd_num_cells floats (u, v, p per cell), exactly as an
+ * iteration applies it (Schur prediction, V-cycle or Jacobi relaxation by
+ * precond_type, velocity correction) on the matrices of the last assembly.
+ * Uses the first Krylov basis / Z slots and the pressure scratch, all of which
+ * the next solve rewrites before reading: a later step keeps its bits.  Needs
+ * a completed step (and, with precond_type 1, a built hierarchy); debug/parity
+ * only; one GPU only (else CFD_ERR_INVALID).                                 */
+cfd_status cfd_debug_apply_precond(cfd_solver* s, const float* v, float* z, size_t n3);
 /* Layout-true bytes of one level-0 smoother sweep: the minimum the kernel
  * moves in this library's level image (u8 lengths, ELL values + 16/32-bit
  * columns, b, x, diagonal, x_out); the roofline of record divides this by

@@ -1749,4 +1749,70 @@ int oracle_amg_levels(const oracle_solver* s, int* num_levels, uint32_t* rows, u
   return 0;
 }
 
+// cfd_debug_amg_level on the oracle's levels: A as stored, dv / de as
+// smooth_rows reads them, agg = P's column, R's rows, and the first four
+// members of each aggregate listed from R.
+int oracle_debug_amg_level(oracle_solver* s, int level, cfd_amg_level* io) {
+  if (!s->amg) return fail("no AMG hierarchy built yet");
+  if (!io || level < 0 || level >= (int)s->amg->levels.size()) return fail("no such AMG level");
+  const AmgLevel& L = s->amg->levels[level];
+  const Csr& A = L.A;
+  const uint32_t n = (uint32_t)L.n, nc = L.has_op ? (uint32_t)L.R.rows : 0;
+  const uint64_t nnz = A.col.size(), r_nnz = L.has_op ? L.R.col.size() : 0;
+  const bool fill = io->row || io->col || io->val || io->dv || io->de || io->agg || io->r_row || io->r_col ||
+                    io->m4 || io->m4_more;
+  if (fill && (io->n != n || io->nc != nc || io->nnz != nnz || io->r_nnz != r_nnz))
+    return fail("AMG level read-back: the sizes are not those of the first call");
+  io->n = n;
+  io->nc = nc;
+  io->nnz = nnz;
+  io->r_nnz = r_nnz;
+  io->wide = 0;
+  io->use16 = 0;
+  if (!fill) return 0;
+  if (io->row) std::copy(A.row.begin(), A.row.end(), io->row);
+  if (io->col) std::copy(A.col.begin(), A.col.end(), io->col);
+  if (io->val) std::copy(A.val.begin(), A.val.end(), io->val);
+  for (uint32_t i = 0; i < n; ++i) {
+    float raw = 0.0f;
+    for (uint32_t k = A.row[i]; k < A.row[i + 1]; ++k)
+      if (A.col[k] == i) raw = A.val[k];
+    if (io->dv) io->dv[i] = raw;
+    if (io->de) io->de[i] = std::fabs(raw) < 1e-14f ? 1.0f : raw;
+  }
+  if (!nc) return 0;
+  for (uint32_t i = 0; i < n && io->agg; ++i) {
+    if (L.P.row[i + 1] - L.P.row[i] != 1) return fail("AMG level read-back: a row without its aggregate");
+    io->agg[i] = L.P.col[L.P.row[i]];
+  }
+  if (io->r_row) std::copy(L.R.row.begin(), L.R.row.end(), io->r_row);
+  if (io->r_col) std::copy(L.R.col.begin(), L.R.col.end(), io->r_col);
+  for (uint32_t I = 0; I < nc; ++I) {
+    const uint32_t k0 = L.R.row[I], m = L.R.row[I + 1] - k0;
+    for (uint32_t q = 0; q < 4 && io->m4; ++q) io->m4[4 * (size_t)I + q] = q < m ? (int32_t)L.R.col[k0 + q] : -1;
+    if (io->m4_more) io->m4_more[I] = m > 4 ? 1 : 0;
+  }
+  return 0;
+}
+
+// cfd_debug_amg_vcycle: the cycle apply_precond runs, on (p_sol, temp_p)
+int oracle_debug_amg_vcycle(oracle_solver* s, const float* x0, const float* b, float* x_out, size_t n) {
+  if (!s->amg || !s->fgmres_init) return fail("no AMG hierarchy built yet");
+  if (n != s->N || !x0 || !b || !x_out) return fail("AMG V-cycle call: vectors of num_cells floats");
+  std::copy(x0, x0 + n, s->p_sol.begin());
+  std::copy(b, b + n, s->temp_p.begin());
+  s->amg->v_cycle(s->p_sol.data(), s->temp_p.data());
+  std::copy(s->p_sol.begin(), s->p_sol.end(), x_out);
+  return 0;
+}
+
+// cfd_debug_apply_precond: apply_precond on the last assembly's matrices
+int oracle_debug_apply_precond(oracle_solver* s, const float* v, float* z, size_t n3) {
+  if (!s->fgmres_init) return fail("preconditioner call: no step solved yet");
+  if (s->constants.precond_type == 1 && !s->amg) return fail("no AMG hierarchy built yet");
+  if (n3 != 3 * (size_t)s->N || !v || !z) return fail("preconditioner call: vectors of 3 num_cells floats");
+  apply_precond(s, v, z);
+  return 0;
+}
+
 }  // extern "C"

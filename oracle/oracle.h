@@ -61,6 +61,12 @@ size_t oracle_debug_buffer_len(const oracle_solver* s, int id);
 int oracle_debug_buffer(oracle_solver* s, int id, float* out, size_t count);
 int oracle_debug_prepare_assemble(oracle_solver* s, int assemble);
 int oracle_amg_levels(const oracle_solver* s, int* num_levels, uint32_t* rows, uint64_t* nnz);
+/* Mirrors of cfd_debug_amg_level (two calls: sizes, then arrays) and
+ * cfd_debug_amg_vcycle on the oracle's own hierarchy; 1 when none is built.  */
+int oracle_debug_amg_level(oracle_solver* s, int level, cfd_amg_level* io);
+int oracle_debug_amg_vcycle(oracle_solver* s, const float* x0, const float* b, float* x_out, size_t n);
+/* Mirror of cfd_debug_apply_precond: z = M^-1 v by apply_precond.           */
+int oracle_debug_apply_precond(oracle_solver* s, const float* v, float* z, size_t n3);
 const char* oracle_last_error(void);
 
 #ifdef __cplusplus

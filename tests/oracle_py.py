@@ -52,6 +52,10 @@ def olib():
         L.oracle_debug_prepare_assemble.argtypes = [vp, C.c_int]
         L.oracle_amg_levels.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint64)]
+        L.oracle_debug_amg_level.argtypes = [vp, C.c_int, C.POINTER(_ffi.AmgLevel)]
+        L.oracle_debug_amg_vcycle.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), C.c_size_t]
+        L.oracle_debug_apply_precond.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
         L.oracle_last_error.restype = C.c_char_p
         L.oracle_set_semantics.argtypes = [vp, C.c_int]
         _olib = L
@@ -204,6 +208,29 @@ class OracleSolver:
 
     def debug_prepare_assemble(self, assemble=True):
         olib().oracle_debug_prepare_assemble(self._h, 1 if assemble else 0)
+
+    def debug_apply_precond(self, v) -> np.ndarray:
+        v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        assert v.size == 3 * self.num_cells
+        z = np.zeros(v.size, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _ck(olib().oracle_debug_apply_precond(self._h, v.ctypes.data_as(fp), z.ctypes.data_as(fp), v.size),
+            "debug_apply_precond")
+        return z
+
+    def debug_amg_level(self, level: int) -> dict:
+        return _ffi.amg_level_readback(
+            lambda p: _ck(olib().oracle_debug_amg_level(self._h, int(level), p), "debug_amg_level"))
+
+    def debug_amg_vcycle(self, x0, b) -> np.ndarray:
+        x0 = np.ascontiguousarray(x0, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        assert x0.shape == b.shape == (self.num_cells,)
+        out = np.zeros(self.num_cells, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _ck(olib().oracle_debug_amg_vcycle(self._h, x0.ctypes.data_as(fp), b.ctypes.data_as(fp),
+                                           out.ctypes.data_as(fp), self.num_cells), "debug_amg_vcycle")
+        return out
 
     def amg_levels(self):
         nl = C.c_int()
