@@ -14,15 +14,12 @@ namespace cfd2 {
 
 namespace {
 
-constexpr uint32_t kBlockCells = 4 * kRedChunkCells;  // one block: 4 chunks of 256 cells
-
 // The blocks are remapped per XCD (xcd_block): XCD k sweeps a contiguous range
 // of cells, so the u[other] gathers hit its L2.  Order only.
-// Thread t of block b handles cells b*1024 + q*256 + t, q = 0..3 (every load of
-// a face slot is one coalesced wavefront access): chunk q of the block is its
-// 256 cells of round q, wavefront w the chunk's quarter w.  Sums: the
-// quarter's shuffle tree, the chunk's 4 quarters pairwise, then the block's
-// units of U chunks -- the tree of k_evolution_partial.  Maxima as bit
+// A block takes kRedBlockCells cells (kernels.hpp; every load of a face slot
+// is one coalesced wavefront access): chunk q of the block is its 256 cells of
+// round q, wavefront w the chunk's quarter w.  Sums: the quarter's shuffle
+// tree, then unit_partials -- the tree of k_evolution_partial.  Maxima as bit
 // patterns (non-negative values order as unsigned integers; a NaN counts 0).
 template <bool FIELDS, bool FORCE>
 __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
@@ -35,7 +32,7 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   unsigned long long ms = 0, mo = 0, md = 0;
   for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kBlockCells + q * kRedChunkCells + threadIdx.x;
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
     double t[kFlowDiagSums];
 #pragma unroll
     for (int f = 0; f < kFlowDiagSums; ++f) t[f] = 0.0;
@@ -145,55 +142,18 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
     lmax[2][w] = md;
   }
   __syncthreads();
-  const uint32_t U = a.U, UB = 4 / U;
-  if (threadIdx.x < kFlowDiagSums * UB) {
-    const uint32_t f = threadIdx.x / UB, u = threadIdx.x % UB, unit = lb * UB + u;
-    double ch[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ch[q] = (lsum[f][q][0] + lsum[f][q][1]) + (lsum[f][q][2] + lsum[f][q][3]);
-    const double v = U == 4 ? (ch[0] + ch[1]) + (ch[2] + ch[3]) : (U == 2 ? ch[2 * u] + ch[2 * u + 1] : ch[u]);
-    if ((uint64_t)unit * U * kRedChunkCells < N && unit < a.np) a.partial[(size_t)f * a.np + unit] = v;
-  }
+  const uint32_t UB = 4 / a.U, f = threadIdx.x / UB;  // thread f UB + u: unit u of sum f
+  if (f < kFlowDiagSums) unit_partials(lsum[f], a.U, a.np, N, lb, a.partial + (size_t)f * a.np, threadIdx.x % UB);
   if (threadIdx.x >= 64 && threadIdx.x < 67) {
     const uint32_t j = threadIdx.x - 64;
-    const unsigned long long m01 = lmax[j][0] > lmax[j][1] ? lmax[j][0] : lmax[j][1];
-    const unsigned long long m23 = lmax[j][2] > lmax[j][3] ? lmax[j][2] : lmax[j][3];
-    a.blockmax[3 * (size_t)lb + j] = m01 > m23 ? m01 : m23;
-  }
-}
-
-// folds the per-block maxima: out[j] = max over blocks of blockmax[3 b + j]
-__global__ void __launch_bounds__(kBlock) k_flow_diag_max(const unsigned long long* __restrict__ blockmax,
-                                                          uint32_t nb, unsigned long long* out) {
-  __shared__ unsigned long long lmax[3][4];
-  unsigned long long m[3] = {0, 0, 0};
-  for (uint32_t b = threadIdx.x; b < nb; b += kBlock) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const unsigned long long v = blockmax[3 * (size_t)b + j];
-      m[j] = v > m[j] ? v : m[j];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    m[j] = wave_max(m[j]);
-    if ((threadIdx.x & 63) == 0) lmax[j][threadIdx.x >> 6] = m[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const uint32_t j = threadIdx.x;
-    const unsigned long long m01 = lmax[j][0] > lmax[j][1] ? lmax[j][0] : lmax[j][1];
-    const unsigned long long m23 = lmax[j][2] > lmax[j][3] ? lmax[j][2] : lmax[j][3];
-    out[j] = m01 > m23 ? m01 : m23;
+    a.blockmax[3 * (size_t)lb + j] = block_of4_max(lmax[j]);
   }
 }
 
 }  // namespace
 
-uint32_t flow_diag_blocks(uint32_t N) { return (uint32_t)(((uint64_t)N + kBlockCells - 1) / kBlockCells); }
-
 void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s) {
-  const uint32_t nb = flow_diag_blocks(a.N);
+  const uint32_t nb = red_blocks(a.N);
   if (nb) {
     const bool fields = a.omega_out != nullptr, force = a.wall_mask != nullptr;
     const dim3 g(nb), b(kBlock);
@@ -206,7 +166,7 @@ void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStre
     else
       hipLaunchKernelGGL((k_flow_diag<false, false>), g, b, 0, s, a);
   }
-  hipLaunchKernelGGL(k_flow_diag_max, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, maxout);
+  hipLaunchKernelGGL(k_block_fold<unsigned long long>, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, 3u, 0u, maxout);
 }
 
 }  // namespace cfd2

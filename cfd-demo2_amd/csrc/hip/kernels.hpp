@@ -16,6 +16,7 @@
 //    the same rounding as the reference's `scale` pass, which is thereby gone).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -53,6 +54,13 @@ constexpr uint32_t kMetaTSlotShift = 16;       // its slot in the coupled-matrix
 constexpr uint32_t kRedChunkCells = 256;
 constexpr uint32_t kRedMaxSegLog2 = 8;
 constexpr uint32_t kRedMaxSegments = 4096;  // the total's tree runs in LDS (N <= 268 M cells)
+// A 256-thread block of a chunk kernel takes 4 chunks: thread t of block b
+// handles cells b * kRedBlockCells + q * kRedChunkCells + t, q = 0..3.
+constexpr uint32_t kRedBlockCells = 4 * kRedChunkCells;
+// Its grid.  ceil(ceil(N / 256) / 4) == ceil(N / 1024) for every N, and the
+// 32-bit N + 1023 cannot wrap: the solver refuses meshes above 2^28 cells
+// (kRedMaxSegments segments of at most 2^16 cells).
+inline uint32_t red_blocks(uint32_t N) { return (N + kRedBlockCells - 1) / kRedBlockCells; }
 
 struct RedGeom {
   uint32_t g = 0;          // log2 chunks per segment
@@ -512,9 +520,8 @@ struct FlowDiagArgs {
   uint32_t U;                 // chunks per unit (RedGeom::U)
   uint32_t np;                // unit partials per sum
   double* partial;            // [kFlowDiagSums * np]
-  unsigned long long* blockmax;  // [3 * flow_diag_blocks(N)] scratch
+  unsigned long long* blockmax;  // [3 * red_blocks(N)] scratch
 };
-uint32_t flow_diag_blocks(uint32_t N);
 // maxout[0..2] = bits of max s (f64), max |omega|, max |div| (f32 bits, zero-extended)
 void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s);
 
@@ -555,6 +562,9 @@ struct ScalarGradArgs {
   const float* phi_old;  // [N]
   float inlet_value;
   float2* g;             // [N]
+  // the field the assembly `a` is for
+  ScalarGradArgs(const ScalarAssembleArgs& a, float2* g_)
+      : N(a.N), fs(a.fs), vol(a.vol), phi_old(a.phi_old), inlet_value(a.inlet_value), g(g_) {}
 };
 void launch_scalar_grad(const ScalarGradArgs& a, hipStream_t s);
 struct ScalarLimitedArgs {
@@ -563,10 +573,13 @@ struct ScalarLimitedArgs {
   uint32_t* clamped;  // one word: += the cells whose t the clamp changed (the caller zeroes it)
 };
 void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s);
-// One Jacobi sweep: phi_out_i = (b_i + sum over internal slots k of c_k *
-// phi_in[other_k]) / diag_i, the sum starting from b_i, a true division.  The
-// columns are fs.other as it stands (stride N).
-struct ScalarSweepArgs {
+// The assembled system as the solvers read it: the Jacobi row of cell i is
+//   J(phi)_i = (b_i + sum over internal slots k of c_k * phi[other_k]) / diag_i,
+// the sum left to right in slot order (boundary slots skipped), a true
+// division.  The columns are fs.other as it stands (stride N).  It leads both
+// solvers' argument blocks, so its scalars and pointers are the kernel
+// arguments preloaded into SGPRs.
+struct ScalarSystem {
   uint32_t N;
   uint32_t ld;
   const int32_t* other;   // fs.other
@@ -574,19 +587,33 @@ struct ScalarSweepArgs {
   const float* coef;
   const float* diag;
   const float* b;
+};
+// One Jacobi sweep: phi_out = J(phi_in), the sum starting from b_i.
+struct ScalarSweepArgs {
+  ScalarSystem sys;
   const float* phi_in;
   float* phi_out;
   uint32_t* blockmax;     // [scalar_sweep_blocks(N)] scratch of the delta form
 };
 uint32_t scalar_sweep_blocks(uint32_t N);
+// What the sweep and the statistics leave for the host, one device object.
+struct ScalarResults {
+  uint32_t delta, pad;  // launch_scalar_sweep
+  uint32_t kmin, kmax;  // launch_scalar_stats
+  double integral;      // launch_evolution_final over the statistics' partials
+};
+static_assert(offsetof(ScalarResults, delta) == 0 && offsetof(ScalarResults, kmin) == 8 &&
+                  offsetof(ScalarResults, kmax) == 12 && offsetof(ScalarResults, integral) == 16,
+              "ScalarResults: the words the kernels write");
 // delta != null: the sweep also leaves delta[0] = bits of max_i |phi_out_i -
 // phi_in_i| (non-negative f32 values order as unsigned integers; a NaN
 // difference counts as +inf, 0x7f800000, so it never reads as converged)
 void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s);
 // Read-only statistics of one field: unit partials partial[k] (k < np) of
 // sum (double)vol_i * (double)phi_i in the canonical tree (as k_flow_diag
-// writes its sums), and mm[0], mm[1] = min and max of phi as order-preserving
-// keys (scalar_key_value decodes them; NaN cells are ignored, no cell: NaN).
+// writes its sums), and res->kmin, res->kmax = min and max of phi as
+// order-preserving keys (scalar_key_value decodes them; NaN cells are ignored,
+// no cell: NaN).
 struct ScalarStatsArgs {
   uint32_t N;
   const float* vol;
@@ -594,35 +621,37 @@ struct ScalarStatsArgs {
   uint32_t U;          // chunks per unit (RedGeom::U)
   uint32_t np;         // unit partials
   double* partial;     // [np]
-  uint32_t* blockmm;   // [2 * flow_diag_blocks(N)] scratch
+  uint32_t* blockmm;   // [2 * red_blocks(N)] scratch
 };
-void launch_scalar_stats(const ScalarStatsArgs& a, uint32_t* mm, hipStream_t s);
+void launch_scalar_stats(const ScalarStatsArgs& a, ScalarResults* res, hipStream_t s);
 // BiCGStab on the Jacobi-scaled system of the assembled field (include/
 // cfd2_amd.h "Arithmetic of method 1" is the contract).  The operator and the
-// x / r update run over blocks of 4 chunks (thread t of block b: cells b*1024
-// + q*256 + t, as k_scalar_stats) and leave the unit partials of their dots in
-// partial[v * np + unit] and the block maxima of |r| in blockmax; one-block
-// finishing kernels turn them into the coefficients and the status words.
-// Everything after a stop returns at once: x is frozen.
+// x / r update run over blocks of 4 chunks (kRedBlockCells, as k_scalar_stats)
+// and leave the unit partials of their dots in partial[v * np + unit] and the
+// block maxima of |r| in blockmax; one-block finishing kernels turn them into
+// the coefficients and the status words.  Everything after a stop returns at
+// once: x is frozen.
 constexpr uint32_t kKryDone = 0, kKryReason = 1, kKryIter = 2, kKryRes = 3, kKryMode = 4;  // state words
+// The solver's device state, one object; the finishing kernels write it, the
+// host reads st[0..3] once per batch.
+struct ScalarKrylovState {
+  double dv[4];    // rho, alpha, omega in f64
+  uint32_t st[8];  // done, reason, iteration, bits of max |r|, mode of the x / r update
+  float co[4];     // alpha, omega, beta rounded to f32
+};
+static_assert(offsetof(ScalarKrylovState, dv) == 0 && offsetof(ScalarKrylovState, st) == 32 &&
+                  offsetof(ScalarKrylovState, co) == 64,
+              "ScalarKrylovState: the words the kernels write");
 struct ScalarKrylovArgs {
-  uint32_t N;
-  uint32_t ld;
-  const int32_t* other;   // fs.other
-  const uint32_t* nface;  // fs.nface
-  const float* coef;
-  const float* diag;
-  const float* b;
+  ScalarSystem sys;
   float* x;               // [N] phi_old on entry, the frozen iterate after the stop
   float *rh, *r, *p, *v, *s, *t;  // [N] work vectors
   uint32_t U;             // chunks per unit (RedGeom::U)
   uint32_t np;            // unit partials per dot
   double* partial;        // [2 * np]
-  uint32_t* blockmax;     // [flow_diag_blocks(N)]
-  double* dv;             // [4] rho, alpha, omega in f64
-  uint32_t* st;           // [8] done, reason, iteration, bits of max |r|, mode of the x / r update
-  float* co;              // [4] alpha, omega, beta rounded to f32
-  RedSrcD red;            // combine(partial, 2)
+  uint32_t* blockmax;     // [red_blocks(N)]
+  ScalarKrylovState* state;
+  RedSrcD red;           // combine(partial, 2)
   float tol;
 };
 // r = rh = p = J(x) - x, rho, max |r|; the state words (stop with reason 1 at

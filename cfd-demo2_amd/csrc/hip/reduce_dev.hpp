@@ -253,22 +253,80 @@ __device__ __forceinline__ float unit_value_q(const float* ql, uint32_t U, uint3
   for (int q = 0; q < 4; ++q) l[q] = quarter_chunk(ql, q);
   return unit_value(l, U, u);
 }
+// The block's unit partials of one sum from its quarter values l[chunk q][quarter
+// w] (after the barrier): thread u < 4 / U forms unit u -- the chunks' quarters
+// pairwise, then unit_value -- and stores it to dst[unit] if the unit starts
+// inside the mesh.  A kernel with several sums picks the thread of each (sum, u).
+__device__ __forceinline__ void unit_partials(const double (*l)[4], uint32_t U, uint32_t np, uint32_t N, uint32_t lb,
+                                              double* dst, uint32_t u = threadIdx.x) {
+  const uint32_t UB = 4 / U;
+  if (u >= UB) return;
+  const uint32_t unit = lb * UB + u;
+  double ch[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ch[q] = (l[q][0] + l[q][1]) + (l[q][2] + l[q][3]);
+  const double v = unit_value(ch, U, u);
+  if ((uint64_t)unit * U * kRedChunkCells < N && unit < np) dst[unit] = v;
+}
 // the block's chunks are all inside the mesh
 __device__ __forceinline__ bool block_full(uint32_t N, uint32_t b = ~0u) {
-  return (size_t)((b == ~0u ? blockIdx.x : b) + 1) * 4u * kRedChunkCells <= N;
-}
-// maximum over the wavefront of non-negative values' bit patterns (every lane)
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long w = (unsigned long long)__shfl_xor((long long)v, o);
-    v = w > v ? w : v;
-  }
-  return v;
+  return (size_t)((b == ~0u ? blockIdx.x : b) + 1) * kRedBlockCells <= N;
 }
 
-inline unsigned red_blocks(uint32_t N) {  // 4 chunks of 256 cells per 256-thread block
-  const unsigned nch = (N + kRedChunkCells - 1) / kRedChunkCells;
-  return (nch + 3) / 4;
+// ---- maxima and minima as unsigned integers ----
+// Non-negative floats order as their bit patterns, every non-NaN float as its
+// scalar_value_key; an integer maximum is exact in any order, so none of the
+// trees below is part of a result's definition.
+// |v| as such a pattern; a NaN counts as +inf, so it is never the smaller one
+constexpr uint32_t kDeltaNaN = 0x7f800000u;
+__device__ __forceinline__ uint32_t abs_bits(float v) {
+  const float d = fabsf(v);
+  return d == d ? __float_as_uint(d) : kDeltaNaN;
+}
+template <bool MIN, class T>
+__device__ __forceinline__ T ext(T a, T b) {
+  return (MIN ? b < a : b > a) ? b : a;
+}
+// over the wavefront (the xor butterfly: every lane holds the result)
+template <bool MIN, class T>
+__device__ __forceinline__ T wave_ext(T v) {
+  for (int o = 32; o >= 1; o >>= 1) v = ext<MIN>(v, (T)__shfl_xor(v, o));
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T v) { return wave_ext<false>(v); }
+template <class T>
+__device__ __forceinline__ T wave_min(T v) { return wave_ext<true>(v); }
+// over a 256-thread block, from its four wavefronts' values in LDS (after the barrier)
+static_assert(kBlock == 4 * 64, "block_of4_*: four wavefronts per block");
+template <bool MIN, class T>
+__device__ __forceinline__ T block_of4_ext(const T* l) {
+  return ext<MIN>(ext<MIN>(l[0], l[1]), ext<MIN>(l[2], l[3]));
+}
+template <class T>
+__device__ __forceinline__ T block_of4_max(const T* l) { return block_of4_ext<false>(l); }
+template <class T>
+__device__ __forceinline__ T block_of4_min(const T* l) { return block_of4_ext<true>(l); }
+
+// One block folds per-block values: out[j] = the minimum (j < nmin) or maximum
+// over the blocks b < nb of v[nv b + j], j < nv (no block: the neutral element).
+template <class T>
+__global__ void __launch_bounds__(kBlock) k_block_fold(const T* __restrict__ v, uint32_t nb, uint32_t nv, uint32_t nmin,
+                                                       T* out) {
+  __shared__ T l[kBlock / 64];
+  for (uint32_t j = 0; j < nv; ++j) {
+    const bool mn = j < nmin;
+    T m = mn ? ~T(0) : T(0);
+    for (uint32_t b = threadIdx.x; b < nb; b += kBlock) {
+      const T x = v[(size_t)nv * b + j];
+      m = mn ? ext<true>(m, x) : ext<false>(m, x);
+    }
+    m = mn ? wave_min(m) : wave_max(m);
+    if (red_lane() == 0) l[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) out[j] = mn ? block_of4_min(l) : block_of4_max(l);
+    __syncthreads();
+  }
 }
 
 }  // namespace cfd2

@@ -3,6 +3,17 @@
 // left in flux_s (and, for a field on scheme 1, the gradient pass and the
 // limited right-hand side), one Jacobi sweep over its slot-major ELL image, and
 // the read-only field statistics.  Nothing the step reads is written.
+//
+// The pieces the kernels share, each written once:
+//   slots4        four slots of a cell from one slot-major array, the loads in
+//                 flight together (the gradient, the limited assembly, the row)
+//   scalar_coef   one slot's coefficient (both assemblies: the same bits)
+//   scalar_row    the Jacobi row sum of kernels.hpp ScalarSystem (the sweep
+//                 and the BiCGStab operator)
+//   reduce_dev.hpp: unit_partials (a block's sums), wave_max / block_of4_max
+//                 (its maxima), k_block_fold (the maxima of all blocks)
+// The sweep and the pointwise kernels run thread per cell (row_id); the kernels
+// that sum run over blocks of kRedBlockCells cells, chunk by chunk.
 #include <hip/hip_runtime.h>
 
 #include "device_util.hpp"
@@ -13,8 +24,22 @@ namespace cfd2 {
 
 namespace {
 
-constexpr uint32_t kStatCells = 4 * kRedChunkCells;  // k_scalar_stats: one block, 4 chunks of 256 cells
-constexpr uint32_t kDeltaNaN = 0x7f800000u;          // a NaN difference counts as +inf
+// Slots k0 .. k0 + 3 of cell i from a slot-major array of row stride ld: four
+// coalesced wavefront loads; a slot >= nf is `off` and loads nothing.
+template <bool NT = false, class T>
+__device__ __forceinline__ void slots4(const T* p, uint32_t ld, uint32_t i, uint32_t k0, uint32_t nf, T off,
+                                       T (&v)[4]) {
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) v[j] = k0 + j < nf ? ldx<NT>(p + ((size_t)(k0 + j) * ld + i)) : off;
+}
+
+// One slot's coefficient: diff = (density * D) * area / dist_e, cin = max(-F, 0),
+// c = cin + diff, in this order (tests/scalar_ref.py restates it)
+__device__ __forceinline__ float scalar_coef(float rd, float F, float area, float dist_e) {
+  const float diff = rd * area / dist_e;
+  const float cin = F < 0.0f ? -F : 0.0f;
+  return cin + diff;
+}
 
 // Thread per cell (row_id: blocks remapped per XCD), every slot load one
 // coalesced wavefront access.
@@ -33,14 +58,7 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a
     const uint32_t bt = fs.meta[e] & kMetaBtypeMask;
     const bool internal = fs.other[e] != kNoCell;
     float c = 0.0f;  // wall: zero flux; outlet: zero gradient, flux >= 0 by construction
-    if (internal || bt == 1u) {
-      const float F = a.flux_s[e];  // mass flux out of this cell
-      // the order is fixed (tests/scalar_ref.py restates it): diff = (density *
-      // D) * area / dist_e, cin = max(-F, 0), c = cin + diff
-      const float diff = rd * fs.area[e] / fs.dist_e[e];
-      const float cin = F < 0.0f ? -F : 0.0f;
-      c = cin + diff;
-    }
+    if (internal || bt == 1u) c = scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]);  // flux_s: out of this cell
     a.coef[(size_t)k * a.ld + i] = c;
     diag += c;
     if (!internal && bt == 1u) b += c * a.inlet_value;
@@ -51,9 +69,8 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a
 
 // ---- scheme 1, "limited linear" (kernels.hpp ScalarGradArgs / ScalarLimitedArgs) ----
 // The Green-Gauss gradient of phi_old, thread per cell: the face values of
-// prepare_cell's vfu branch (flux.hip), the slots four at a time as
-// k_scalar_sweep takes them (the coalesced slot loads, then the four gathers in
-// flight together), the sums in slot order; one 8-byte store.
+// prepare_cell's vfu branch (flux.hip), the slots four at a time (slots4, then
+// the four gathers in flight together), the sums in slot order; one 8-byte store.
 __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
@@ -67,17 +84,12 @@ __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
     int32_t o[4];
     uint32_t mt[4];
     float ar[4], nx[4], ny[4], lam[4], po[4];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-      const bool on = k0 + j < nf;
-      const size_t e = (size_t)(k0 + j) * N + i;
-      o[j] = on ? fs.other[e] : kNoCell;
-      mt[j] = on ? fs.meta[e] : 0u;
-      ar[j] = on ? fs.area[e] : 0.0f;
-      nx[j] = on ? fs.nx[e] : 0.0f;
-      ny[j] = on ? fs.ny[e] : 0.0f;
-      lam[j] = on ? fs.lam_s[e] : 0.0f;
-    }
+    slots4(fs.other, N, i, k0, nf, kNoCell, o);
+    slots4(fs.meta, N, i, k0, nf, 0u, mt);
+    slots4(fs.area, N, i, k0, nf, 0.0f, ar);
+    slots4(fs.nx, N, i, k0, nf, 0.0f, nx);
+    slots4(fs.ny, N, i, k0, nf, 0.0f, ny);
+    slots4(fs.lam_s, N, i, k0, nf, 0.0f, lam);
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) po[j] = o[j] != kNoCell ? a.phi_old[o[j]] : 0.0f;
 #pragma unroll
@@ -93,13 +105,6 @@ __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
     }
   }
   a.g[i] = make_float2(gx / vol, gy / vol);
-}
-
-// One slot's coefficient, the expression of k_scalar_assemble
-__device__ __forceinline__ float scalar_coef(float rd, float F, float area, float dist_e) {
-  const float diff = rd * area / dist_e;
-  const float cin = F < 0.0f ? -F : 0.0f;
-  return cin + diff;
 }
 
 // k_scalar_assemble with the limited right-hand side: the same coef and diag;
@@ -129,18 +134,13 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
       uint32_t mt[4];
       float F[4], ar[4], de[4], dx[4], dy[4], po[4];
       float2 go[4];
-#pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) {
-        const bool on = k0 + j < nf;
-        const size_t e = (size_t)(k0 + j) * N + i;
-        o[j] = on ? fs.other[e] : kNoCell;
-        mt[j] = on ? fs.meta[e] : 0u;
-        F[j] = on ? a.flux_s[e] : 0.0f;
-        ar[j] = on ? fs.area[e] : 0.0f;
-        de[j] = on ? fs.dist_e[e] : 1.0f;
-        dx[j] = on ? fs.dvx[e] : 0.0f;
-        dy[j] = on ? fs.dvy[e] : 0.0f;
-      }
+      slots4(fs.other, N, i, k0, nf, kNoCell, o);
+      slots4(fs.meta, N, i, k0, nf, 0u, mt);
+      slots4(a.flux_s, N, i, k0, nf, 0.0f, F);
+      slots4(fs.area, N, i, k0, nf, 0.0f, ar);
+      slots4(fs.dist_e, N, i, k0, nf, 1.0f, de);
+      slots4(fs.dvx, N, i, k0, nf, 0.0f, dx);
+      slots4(fs.dvy, N, i, k0, nf, 0.0f, dy);
 #pragma unroll
       for (uint32_t j = 0; j < 4; ++j) {
         const bool in = o[j] != kNoCell;
@@ -203,97 +203,54 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
   }
 }
 
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
-    v = w > v ? w : v;
+// The Jacobi row sum of cell i (kernels.hpp ScalarSystem) over the vector `in`,
+// from sum0: the slots four at a time -- the four column and coefficient
+// loads, then the four gathers, in flight together -- and the sum itself left
+// to right in slot order.  NT: the matrix streams are loaded nontemporally.
+template <bool NT>
+__device__ __forceinline__ float scalar_row(const int32_t* other, const float* coef, uint32_t N, uint32_t ld,
+                                            uint32_t nf, uint32_t i, const float* in, float s) {
+  for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
+    int32_t o[4];
+    float c[4], p[4];
+    slots4<NT>(other, N, i, k0, nf, kNoCell, o);
+    slots4<NT>(coef, ld, i, k0, nf, 0.0f, c);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) p[j] = o[j] != kNoCell ? in[o[j]] : 0.0f;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+      if (o[j] != kNoCell) s += c[j] * p[j];  // boundary slots are skipped
   }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
-    v = w < v ? w : v;
-  }
-  return v;
+  return s;
 }
 
-// One Jacobi sweep, thread per cell.  The slots are taken four at a time: the
-// four column / coefficient loads, then the four gathers, are in flight
-// together; the sum itself stays left to right in slot order from b_i.
+// One Jacobi sweep, thread per cell: scalar_row from b_i, a true division.
 // DELTA: also the block's maximum of |phi_out - phi_in| as a bit pattern.
 template <bool DELTA>
 __global__ void __launch_bounds__(kBlock) k_scalar_sweep(ScalarSweepArgs a) {
   __shared__ uint32_t lmax[kBlock / 64];
-  const uint32_t N = a.N;
+  const ScalarSystem& m = a.sys;
+  const uint32_t N = m.N;
   const uint32_t lb = xcd_block();
   const uint32_t i = lb * kBlock + threadIdx.x;
   uint32_t bits = 0;
   if (i < N) {
-    float s = a.b[i];
-    const float dg = a.diag[i];
-    const uint32_t nf = a.nface[i];
-    for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
-      int32_t o[4];
-      float c[4], p[4];
-#pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t k = k0 + j;
-        const bool on = k < nf;
-        o[j] = on ? a.other[(size_t)k * N + i] : kNoCell;
-        c[j] = on ? a.coef[(size_t)k * a.ld + i] : 0.0f;
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) p[j] = o[j] != kNoCell ? a.phi_in[o[j]] : 0.0f;
-#pragma unroll
-      for (uint32_t j = 0; j < 4; ++j)
-        if (o[j] != kNoCell) s += c[j] * p[j];  // boundary slots are skipped
-    }
-    const float v = s / dg;
+    const float b = m.b[i];
+    const float dg = m.diag[i];
+    const float v = scalar_row<false>(m.other, m.coef, N, m.ld, m.nface[i], i, a.phi_in, b) / dg;
     a.phi_out[i] = v;
-    if constexpr (DELTA) {
-      const float d = fabsf(v - a.phi_in[i]);
-      bits = d == d ? __float_as_uint(d) : kDeltaNaN;
-    }
+    if constexpr (DELTA) bits = abs_bits(v - a.phi_in[i]);
   }
   if constexpr (DELTA) {
-    bits = wave_max32(bits);
-    if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = bits;
+    bits = wave_max(bits);
+    if (red_lane() == 0) lmax[threadIdx.x >> 6] = bits;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint32_t m01 = lmax[0] > lmax[1] ? lmax[0] : lmax[1];
-      const uint32_t m23 = lmax[2] > lmax[3] ? lmax[2] : lmax[3];
-      a.blockmax[lb] = m01 > m23 ? m01 : m23;
-    }
+    if (threadIdx.x == 0) a.blockmax[lb] = block_of4_max(lmax);
   }
 }
 
-// folds per-block values: out[j] = min (j < nmin) or max over blocks of v[nv b + j]
-__global__ void __launch_bounds__(kBlock) k_scalar_fold(const uint32_t* __restrict__ v, uint32_t nb, uint32_t nv,
-                                                        uint32_t nmin, uint32_t* out) {
-  __shared__ uint32_t l[kBlock / 64];
-  for (uint32_t j = 0; j < nv; ++j) {
-    const bool mn = j < nmin;
-    uint32_t m = mn ? ~0u : 0u;
-    for (uint32_t b = threadIdx.x; b < nb; b += kBlock) {
-      const uint32_t x = v[(size_t)nv * b + j];
-      m = mn ? (x < m ? x : m) : (x > m ? x : m);
-    }
-    m = mn ? wave_min32(m) : wave_max32(m);
-    if ((threadIdx.x & 63) == 0) l[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t r = l[0];
-      for (uint32_t w = 1; w < kBlock / 64; ++w) r = mn ? (l[w] < r ? l[w] : r) : (l[w] > r ? l[w] : r);
-      out[j] = r;
-    }
-    __syncthreads();
-  }
-}
-
-// Field statistics, the shape of k_flow_diag: thread t of block b handles cells
-// b*1024 + q*256 + t, q = 0..3; the sum's tree is the quarter's shuffle tree,
-// the chunk's 4 quarters pairwise, then the block's units of U chunks.
+// Field statistics, the shape of k_flow_diag: blocks of kRedBlockCells cells;
+// the sum's tree is the quarter's shuffle tree, then unit_partials.
 __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
   __shared__ double lsum[4][4];  // [chunk q][quarter w]
   __shared__ uint32_t lmm[2][4];
@@ -302,7 +259,7 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint32_t kmin = ~0u, kmax = 0u;
   for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kStatCells + q * kRedChunkCells + threadIdx.x;
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
     double t = 0.0;
     if (ci < N) {
       const float ph = a.phi[ci];
@@ -316,30 +273,17 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
     const double r = wave_tree(t);
     if (lane == 0) lsum[q][w] = r;
   }
-  kmin = wave_min32(kmin);
-  kmax = wave_max32(kmax);
+  kmin = wave_min(kmin);
+  kmax = wave_max(kmax);
   if (lane == 0) {
     lmm[0][w] = kmin;
     lmm[1][w] = kmax;
   }
   __syncthreads();
-  const uint32_t U = a.U, UB = 4 / U;
-  if (threadIdx.x < UB) {
-    const uint32_t u = threadIdx.x, unit = lb * UB + u;
-    double ch[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ch[q] = (lsum[q][0] + lsum[q][1]) + (lsum[q][2] + lsum[q][3]);
-    const double v = unit_value(ch, U, u);
-    if ((uint64_t)unit * U * kRedChunkCells < N && unit < a.np) a.partial[unit] = v;
-  }
+  unit_partials(lsum, a.U, a.np, N, lb, a.partial);
   if (threadIdx.x == 64) {
-    uint32_t mn = lmm[0][0], mx = lmm[1][0];
-    for (int j = 1; j < 4; ++j) {
-      mn = lmm[0][j] < mn ? lmm[0][j] : mn;
-      mx = lmm[1][j] > mx ? lmm[1][j] : mx;
-    }
-    a.blockmm[2 * (size_t)lb] = mn;
-    a.blockmm[2 * (size_t)lb + 1] = mx;
+    a.blockmm[2 * (size_t)lb] = block_of4_min(lmm[0]);
+    a.blockmm[2 * (size_t)lb + 1] = block_of4_max(lmm[1]);
   }
 }
 
@@ -353,63 +297,29 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
 constexpr bool kKryNT = CFD_SCALAR_KRYLOV_NT != 0;
 constexpr int kKryInit = 0, kKryV = 1, kKryT = 2;
 
-__device__ __forceinline__ uint32_t abs_bits(float v) {
-  const float d = fabsf(v);
-  return d == d ? __float_as_uint(d) : kDeltaNaN;
-}
-
-// the block's unit partials of dot v from its quarter values l[chunk q][quarter w]
-__device__ __forceinline__ void kry_units(const ScalarKrylovArgs& a, const double (*l)[4], uint32_t lb, uint32_t v) {
-  const uint32_t U = a.U, UB = 4 / U;
-  if (threadIdx.x < UB) {
-    const uint32_t u = threadIdx.x, unit = lb * UB + u;
-    double ch[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ch[q] = (l[q][0] + l[q][1]) + (l[q][2] + l[q][3]);
-    const double val = unit_value(ch, U, u);
-    if ((uint64_t)unit * U * kRedChunkCells < a.N && unit < a.np) a.partial[(size_t)v * a.np + unit] = val;
-  }
-}
-
 // One operator pass with its dots.  kKryInit: r = rh = p = J(x) - x, <r, r>,
 // the block maximum of |r|.  kKryV: v = A p, <rh, v>.  kKryT: t = A s, <t, s>,
-// <t, t>.  The slots four at a time as k_scalar_sweep takes them.
+// <t, t>.  A p = p - J0(p), J0 = scalar_row from 0 over the diagonal.
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_op(ScalarKrylovArgs a) {
   __shared__ double lsum[2][4][4];  // [dot][chunk q][quarter w]
   __shared__ uint32_t lmax[kBlock / 64];
-  if (MODE != kKryInit && a.st[kKryDone]) return;
-  const uint32_t N = a.N;
+  if (MODE != kKryInit && a.state->st[kKryDone]) return;
+  const ScalarSystem& m = a.sys;
+  const uint32_t N = m.N;
   const uint32_t lb = xcd_block();
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float* __restrict__ in = MODE == kKryInit ? a.x : (MODE == kKryV ? a.p : a.s);
   float* __restrict__ out = MODE == kKryInit ? a.r : (MODE == kKryV ? a.v : a.t);
   uint32_t bits = 0;
   for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kStatCells + q * kRedChunkCells + threadIdx.x;
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
     double t0 = 0.0, t1 = 0.0;
     if (ci < N) {
       const uint32_t i = (uint32_t)ci;
-      float sum = MODE == kKryInit ? ldx<kKryNT>(a.b + i) : 0.0f;
-      const float dg = ldx<kKryNT>(a.diag + i);
-      const uint32_t nf = a.nface[i];
-      for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
-        int32_t o[4];
-        float c[4], g[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t k = k0 + j;
-          const bool on = k < nf;
-          o[j] = on ? ldx<kKryNT>(a.other + ((size_t)k * N + i)) : kNoCell;
-          c[j] = on ? ldx<kKryNT>(a.coef + ((size_t)k * a.ld + i)) : 0.0f;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) g[j] = o[j] != kNoCell ? in[o[j]] : 0.0f;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-          if (o[j] != kNoCell) sum += c[j] * g[j];  // boundary slots are skipped
-      }
-      const float qd = sum / dg;
+      const float sum0 = MODE == kKryInit ? ldx<kKryNT>(m.b + i) : 0.0f;
+      const float dg = ldx<kKryNT>(m.diag + i);
+      const float qd = scalar_row<kKryNT>(m.other, m.coef, N, m.ld, m.nface[i], i, in, sum0) / dg;
       const float own = in[i];
       const float res = MODE == kKryInit ? qd - own : own - qd;
       out[i] = res;
@@ -434,27 +344,23 @@ __global__ void __launch_bounds__(kBlock) k_scalar_krylov_op(ScalarKrylovArgs a)
     }
   }
   if constexpr (MODE == kKryInit) {
-    bits = wave_max32(bits);
+    bits = wave_max(bits);
     if (lane == 0) lmax[w] = bits;
   }
   __syncthreads();
-  kry_units(a, lsum[0], lb, 0);
-  if constexpr (MODE == kKryT) kry_units(a, lsum[1], lb, 1);
+  unit_partials(lsum[0], a.U, a.np, N, lb, a.partial);
+  if constexpr (MODE == kKryT) unit_partials(lsum[1], a.U, a.np, N, lb, a.partial + a.np);
   if constexpr (MODE == kKryInit) {
-    if (threadIdx.x == 64) {
-      const uint32_t m01 = lmax[0] > lmax[1] ? lmax[0] : lmax[1];
-      const uint32_t m23 = lmax[2] > lmax[3] ? lmax[2] : lmax[3];
-      a.blockmax[lb] = m01 > m23 ? m01 : m23;
-    }
+    if (threadIdx.x == 64) a.blockmax[lb] = block_of4_max(lmax);
   }
 }
 
 // s = r - alpha v
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_s(ScalarKrylovArgs a) {
-  if (a.st[kKryDone]) return;
+  if (a.state->st[kKryDone]) return;
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= a.N) return;
-  const float alpha = a.co[0];
+  if (i >= a.sys.N) return;
+  const float alpha = a.state->co[0];
   a.s[i] = a.r[i] - alpha * a.v[i];
 }
 
@@ -463,15 +369,15 @@ __global__ void __launch_bounds__(kBlock) k_scalar_krylov_s(ScalarKrylovArgs a) 
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_xr(ScalarKrylovArgs a) {
   __shared__ double lsum[4][4];
   __shared__ uint32_t lmax[kBlock / 64];
-  const uint32_t mode = a.st[kKryMode];
+  const uint32_t mode = a.state->st[kKryMode];
   if (mode == 2u) return;
-  const uint32_t N = a.N;
+  const uint32_t N = a.sys.N;
   const uint32_t lb = xcd_block();
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float alpha = a.co[0], omega = a.co[1];
+  const float alpha = a.state->co[0], omega = a.state->co[1];
   uint32_t bits = 0;
   for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kStatCells + q * kRedChunkCells + threadIdx.x;
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
     double t0 = 0.0;
     if (ci < N) {
       const uint32_t i = (uint32_t)ci;
@@ -491,23 +397,19 @@ __global__ void __launch_bounds__(kBlock) k_scalar_krylov_xr(ScalarKrylovArgs a)
     const double r0 = wave_tree(t0);
     if (lane == 0) lsum[q][w] = r0;
   }
-  bits = wave_max32(bits);
+  bits = wave_max(bits);
   if (lane == 0) lmax[w] = bits;
   __syncthreads();
-  kry_units(a, lsum, lb, 0);
-  if (threadIdx.x == 64) {
-    const uint32_t m01 = lmax[0] > lmax[1] ? lmax[0] : lmax[1];
-    const uint32_t m23 = lmax[2] > lmax[3] ? lmax[2] : lmax[3];
-    a.blockmax[lb] = m01 > m23 ? m01 : m23;
-  }
+  unit_partials(lsum, a.U, a.np, N, lb, a.partial);
+  if (threadIdx.x == 64) a.blockmax[lb] = block_of4_max(lmax);
 }
 
 // p = r + beta (p - omega v)
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_p(ScalarKrylovArgs a) {
-  if (a.st[kKryDone]) return;
+  if (a.state->st[kKryDone]) return;
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= a.N) return;
-  const float omega = a.co[1], beta = a.co[2];
+  if (i >= a.sys.N) return;
+  const float omega = a.state->co[1], beta = a.state->co[2];
   a.p[i] = a.r[i] + beta * (a.p[i] - omega * a.v[i]);
 }
 
@@ -515,7 +417,7 @@ template <int NT>
 __device__ __forceinline__ uint32_t block_max32(const uint32_t* __restrict__ v, uint32_t nb, uint32_t* l) {
   uint32_t m = 0;
   for (uint32_t b = threadIdx.x; b < nb; b += NT) m = v[b] > m ? v[b] : m;
-  m = wave_max32(m);
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) l[threadIdx.x >> 6] = m;
   __syncthreads();
   uint32_t r = 0;
@@ -539,7 +441,9 @@ __global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKr
                                                                         uint32_t max_iters) {
   __shared__ double la[kRedMaxSegments], lb[65];
   __shared__ uint32_t lm[kRedFinalThreads / 64];
-  uint32_t* st = a.st;
+  uint32_t* st = a.state->st;
+  double* dv = a.state->dv;
+  float* co = a.state->co;
   const uint32_t done = STAGE == kKryFinStart ? 0u : st[kKryDone];
   const uint32_t mode = STAGE == kKryFinBeta ? st[kKryMode] : 0u;
   __syncthreads();  // every thread has read the words thread 0 writes below
@@ -553,23 +457,23 @@ __global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKr
       st[kKryIter] = 0u;
       st[kKryRes] = res;
       st[kKryMode] = 2u;
-      a.dv[0] = rho;
-      a.dv[1] = a.dv[2] = 0.0;
-      a.co[0] = a.co[1] = a.co[2] = 0.0f;
+      dv[0] = rho;
+      dv[1] = dv[2] = 0.0;
+      co[0] = co[1] = co[2] = 0.0f;
     }
   } else if constexpr (STAGE == kKryFinAlpha) {
     if (done) return;
     const double d = red_total<double, kRedFinalThreads>(a.red, 0, la, lb);
     if (threadIdx.x == 0) {
-      const double rho = a.dv[0];
+      const double rho = dv[0];
       const double alpha = rho / d;
       const float af = (float)alpha;
       if (kry_bad(rho) || kry_bad(d) || kry_bad(af)) {
         kry_stop(st, 2u, k);
-        a.co[0] = 0.0f;
+        co[0] = 0.0f;
       } else {
-        a.dv[1] = alpha;
-        a.co[0] = af;
+        dv[1] = alpha;
+        co[0] = af;
       }
     }
   } else if constexpr (STAGE == kKryFinOmega) {
@@ -583,18 +487,18 @@ __global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKr
       if (tt == 0.0) {
         kry_stop(st, 2u, k);
         st[kKryMode] = 1u;
-        a.co[1] = 0.0f;
+        co[1] = 0.0f;
       } else {
         const double omega = ts / tt;
         const float of = (float)omega;
         if (!isfinite(tt) || kry_bad(of)) {
           kry_stop(st, 2u, k);
           st[kKryMode] = 2u;
-          a.co[1] = 0.0f;
+          co[1] = 0.0f;
         } else {
           st[kKryMode] = 0u;
-          a.dv[2] = omega;
-          a.co[1] = of;
+          dv[2] = omega;
+          co[1] = of;
         }
       }
     }
@@ -610,14 +514,14 @@ __global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKr
         return;
       }
       if (k >= max_iters) return;  // the host records reason 3
-      const double beta = (rho1 / a.dv[0]) * (a.dv[1] / a.dv[2]);
+      const double beta = (rho1 / dv[0]) * (dv[1] / dv[2]);
       const float bf = (float)beta;
       if (kry_bad(rho1) || kry_bad(bf)) {
         kry_stop(st, 2u, k + 1u);
-        a.co[2] = 0.0f;
+        co[2] = 0.0f;
       } else {
-        a.dv[0] = rho1;
-        a.co[2] = bf;
+        dv[0] = rho1;
+        co[2] = bf;
       }
     }
   }
@@ -626,13 +530,13 @@ __global__ void __launch_bounds__(kRedFinalThreads) k_scalar_krylov_fin(ScalarKr
 }  // namespace
 
 void launch_scalar_krylov_start(const ScalarKrylovArgs& a, hipStream_t s) {
-  const uint32_t nb = flow_diag_blocks(a.N);
+  const uint32_t nb = red_blocks(a.sys.N);
   if (nb) hipLaunchKernelGGL((k_scalar_krylov_op<kKryInit>), dim3(nb), dim3(kBlock), 0, s, a);
   hipLaunchKernelGGL((k_scalar_krylov_fin<kKryFinStart>), dim3(1), dim3(kRedFinalThreads), 0, s, a, nb, 0u, 0u);
 }
 
 void launch_scalar_krylov_iteration(const ScalarKrylovArgs& a, uint32_t k, uint32_t max_iters, hipStream_t s) {
-  const uint32_t nb = flow_diag_blocks(a.N), ne = grid_for(a.N);
+  const uint32_t nb = red_blocks(a.sys.N), ne = grid_for(a.sys.N);
   if (!nb) return;
   const dim3 one(1), fin(kRedFinalThreads), blk(kBlock);
   hipLaunchKernelGGL((k_scalar_krylov_op<kKryV>), dim3(nb), blk, 0, s, a);
@@ -663,20 +567,21 @@ void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s) {
 }
 
 void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s) {
-  const uint32_t nb = scalar_sweep_blocks(a.N);
+  const uint32_t nb = scalar_sweep_blocks(a.sys.N);
   if (nb) {
     if (delta)
       hipLaunchKernelGGL((k_scalar_sweep<true>), dim3(nb), dim3(kBlock), 0, s, a);
     else
       hipLaunchKernelGGL((k_scalar_sweep<false>), dim3(nb), dim3(kBlock), 0, s, a);
   }
-  if (delta) hipLaunchKernelGGL(k_scalar_fold, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, 1u, 0u, delta);
+  if (delta) hipLaunchKernelGGL(k_block_fold<uint32_t>, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, 1u, 0u, delta);
 }
 
-void launch_scalar_stats(const ScalarStatsArgs& a, uint32_t* mm, hipStream_t s) {
-  const uint32_t nb = flow_diag_blocks(a.N);
+void launch_scalar_stats(const ScalarStatsArgs& a, ScalarResults* res, hipStream_t s) {
+  const uint32_t nb = red_blocks(a.N);
   if (nb) hipLaunchKernelGGL(k_scalar_stats, dim3(nb), dim3(kBlock), 0, s, a);
-  hipLaunchKernelGGL(k_scalar_fold, dim3(1), dim3(kBlock), 0, s, a.blockmm, nb, 2u, 1u, mm);
+  static_assert(offsetof(ScalarResults, kmax) == offsetof(ScalarResults, kmin) + 4, "the fold writes the pair");
+  hipLaunchKernelGGL(k_block_fold<uint32_t>, dim3(1), dim3(kBlock), 0, s, a.blockmm, nb, 2u, 1u, &res->kmin);
 }
 
 }  // namespace cfd2

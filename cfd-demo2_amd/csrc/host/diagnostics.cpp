@@ -28,7 +28,7 @@ bool adaptive_dt_rule(double current_dt, double target_cfl, double min_cell_size
 void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
   const Range range("flow diagnostics");
   CFD_HIP(hipSetDevice(device));
-  const uint32_t nb = flow_diag_blocks(N);
+  const uint32_t nb = red_blocks(N);
   if (!diag_partial) {
     diag_partial = arena.alloc<double>((size_t)kFlowDiagSums * pstride);
     diag_blockmax = arena.alloc<unsigned long long>(3 * (size_t)nb);

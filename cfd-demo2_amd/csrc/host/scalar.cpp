@@ -27,16 +27,18 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   sc_arena.release();
   sc_count = 0;
   sc_alt = sc_coef = sc_diag = sc_b = nullptr;
-  sc_blockmax = sc_res = nullptr;
+  sc_blockmax = nullptr;
+  sc_res = nullptr;
   sc_partial = nullptr;
   for (float*& v : kr_vec) v = nullptr;
-  kr_partial = kr_state = nullptr;
+  kr_partial = nullptr;
+  kr_state = nullptr;
   hr_grad = nullptr;
   hr_count = nullptr;
   for (ScalarField& f : sc_field) f = ScalarField{};
   if (count == 0) return;
   const size_t ld = topo.ld;
-  const size_t nbm = std::max<size_t>(scalar_sweep_blocks(N), 2 * (size_t)flow_diag_blocks(N));
+  const size_t nbm = std::max<size_t>(scalar_sweep_blocks(N), 2 * (size_t)red_blocks(N));
   auto field = [&] {
     float* p = sc_arena.alloc<float>(ld);
     CFD_HIP(hipMemsetAsync(p, 0, ld * sizeof(float), stream));
@@ -48,7 +50,7 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   sc_diag = sc_arena.alloc<float>(ld);
   sc_b = sc_arena.alloc<float>(ld);
   sc_blockmax = sc_arena.alloc<uint32_t>(nbm);
-  sc_res = sc_arena.alloc<uint32_t>(8);
+  sc_res = sc_arena.alloc<ScalarResults>(1);
   sc_partial = sc_arena.alloc<double>(pstride);
   sync();
   sc_cfg = c;
@@ -112,14 +114,7 @@ void Solver::scalar_advance(float dt) {
       // the gradient of phi_old first, every cell before any is read; then the
       // assembly with the limited right-hand side.  The count lands in
       // f.clamped with the first read of the solve below.
-      ScalarGradArgs G{};
-      G.N = N;
-      G.fs = fs;
-      G.vol = d_vol;
-      G.phi_old = f.phi;
-      G.inlet_value = f.par.inlet_value;
-      G.g = hr_grad;
-      launch_scalar_grad(G, stream);
+      launch_scalar_grad(ScalarGradArgs(A, hr_grad), stream);
       CFD_HIP(hipMemsetAsync(hr_count + fi, 0, sizeof(uint32_t), stream));
       launch_scalar_assemble_limited(ScalarLimitedArgs{A, hr_grad, hr_count + fi}, stream);
       check_launch("scalar limited assemble");
@@ -139,29 +134,27 @@ void Solver::scalar_advance(float dt) {
   }
 }
 
+ScalarSystem Solver::scalar_system() const {
+  return ScalarSystem{N, (uint32_t)topo.ld, fs.other, fs.nface, sc_coef, sc_diag, sc_b};
+}
+
 // The Jacobi loop from f.phi, in batches of check_interval sweeps.
 void Solver::scalar_polish(int fi, ScalarField& f) {
   const uint32_t ci = (uint32_t)sc_cfg.check_interval;
   const uint32_t max_sweeps = ((uint32_t)sc_cfg.max_sweeps + ci - 1) / ci * ci;
   ScalarSweepArgs W{};
-  W.N = N;
-  W.ld = topo.ld;
-  W.other = fs.other;
-  W.nface = fs.nface;
-  W.coef = sc_coef;
-  W.diag = sc_diag;
-  W.b = sc_b;
+  W.sys = scalar_system();
   W.blockmax = sc_blockmax;
   uint32_t bits = 0;
   while (f.sweeps < max_sweeps) {
     for (uint32_t k = 0; k < ci; ++k) {  // phi^0 = phi_old; b holds a_t * phi_old, so its buffer is free to swap
       W.phi_in = f.phi;
       W.phi_out = sc_alt;
-      launch_scalar_sweep(W, k + 1 == ci ? sc_res : nullptr, stream);
+      launch_scalar_sweep(W, k + 1 == ci ? &sc_res->delta : nullptr, stream);
       std::swap(f.phi, sc_alt);
     }
     check_launch("scalar sweep");
-    CFD_HIP(hipMemcpyAsync(&bits, sc_res, sizeof(bits), hipMemcpyDeviceToHost, stream));
+    CFD_HIP(hipMemcpyAsync(&bits, &sc_res->delta, sizeof(bits), hipMemcpyDeviceToHost, stream));
     sync();
     f.sweeps += ci;
     std::memcpy(&f.last_delta, &bits, 4);
@@ -182,13 +175,7 @@ void Solver::scalar_polish(int fi, ScalarField& f) {
 // nothing but the number of reads.
 void Solver::scalar_krylov(ScalarField& f) {
   ScalarKrylovArgs K{};
-  K.N = N;
-  K.ld = topo.ld;
-  K.other = fs.other;
-  K.nface = fs.nface;
-  K.coef = sc_coef;
-  K.diag = sc_diag;
-  K.b = sc_b;
+  K.sys = scalar_system();
   K.x = f.phi;
   K.rh = kr_vec[0];
   K.r = kr_vec[1];
@@ -200,15 +187,13 @@ void Solver::scalar_krylov(ScalarField& f) {
   K.np = pstride;
   K.partial = kr_partial;
   K.blockmax = sc_blockmax;
-  K.dv = kr_state;
-  K.st = reinterpret_cast<uint32_t*>(kr_state + 4);
-  K.co = reinterpret_cast<float*>(kr_state + 8);
+  K.state = kr_state;
   K.red = combine(kr_partial, 2);
   K.tol = sc_cfg.tol;
   uint32_t st[4] = {0, 0, 0, 0};
   auto read = [&](const char* where) {
     check_launch(where);
-    CFD_HIP(hipMemcpyAsync(st, K.st, sizeof(st), hipMemcpyDeviceToHost, stream));
+    CFD_HIP(hipMemcpyAsync(st, kr_state->st, sizeof(st), hipMemcpyDeviceToHost, stream));
     sync();
   };
   launch_scalar_krylov_start(K, stream);
@@ -235,7 +220,7 @@ void Solver::set_scalar_solver(int field, const cfd_scalar_solver& c) {
     CFD_HIP(hipSetDevice(device));
     for (float*& v : kr_vec) v = sc_arena.alloc<float>(topo.ld);
     kr_partial = sc_arena.alloc<double>(2 * (size_t)pstride);
-    kr_state = sc_arena.alloc<double>(12);
+    kr_state = sc_arena.alloc<ScalarKrylovState>(1);
   }
   sc_field[field].solver = c;
   sc_field[field].solver.reserved = 0;
@@ -276,13 +261,13 @@ void Solver::scalar_stats(int field, cfd_scalar_stats* out) {
   a.np = pstride;
   a.partial = sc_partial;
   a.blockmm = sc_blockmax;
-  launch_scalar_stats(a, sc_res + 2, stream);
-  launch_evolution_final(combine(sc_partial, 1), reinterpret_cast<double*>(sc_res + 4), stream);
+  launch_scalar_stats(a, sc_res, stream);
+  launch_evolution_final(combine(sc_partial, 1), &sc_res->integral, stream);
   check_launch("scalar stats");
-  uint32_t h[8];
-  CFD_HIP(hipMemcpyAsync(h, sc_res, sizeof(h), hipMemcpyDeviceToHost, stream));
+  ScalarResults h;
+  CFD_HIP(hipMemcpyAsync(&h, sc_res, sizeof(h), hipMemcpyDeviceToHost, stream));
   sync();
-  const uint32_t bmin = scalar_key_value(h[2]), bmax = scalar_key_value(h[3]);
+  const uint32_t bmin = scalar_key_value(h.kmin), bmax = scalar_key_value(h.kmax);
   float vmin, vmax;
   std::memcpy(&vmin, &bmin, 4);
   std::memcpy(&vmax, &bmax, 4);
@@ -293,7 +278,7 @@ void Solver::scalar_stats(int field, cfd_scalar_stats* out) {
   out->dt_used = f.dt_used;
   out->min = vmin;
   out->max = vmax;
-  std::memcpy(&out->integral, h + 4, sizeof(double));
+  out->integral = h.integral;
 }
 
 }  // namespace cfd2

@@ -612,13 +612,13 @@ struct Solver {
   float* sc_diag = nullptr;        // [ld]
   float* sc_b = nullptr;           // [ld]
   uint32_t* sc_blockmax = nullptr; // per-block scratch of the sweep's delta and the stats' min / max
-  uint32_t* sc_res = nullptr;      // [0] delta bits, [2..3] min / max keys, [4..5] the integral (f64)
+  ScalarResults* sc_res = nullptr; // what the sweep and the statistics leave for the host
   double* sc_partial = nullptr;    // [pstride] unit partials of the integral
   // BiCGStab work space, allocated in sc_arena by the first set_scalar_solver
   // that selects method 1 (null before)
   float* kr_vec[6] = {};           // [ld] each: rh, r, p, v, s, t
   double* kr_partial = nullptr;    // [2 * pstride] unit partials of an iteration's dots
-  double* kr_state = nullptr;      // [0..3] rho, alpha, omega (f64); then 8 status words; then alpha, omega, beta (f32)
+  ScalarKrylovState* kr_state = nullptr;
   // Scheme 1 (limited linear) work space, allocated in sc_arena by the first
   // set_scalar_scheme that selects it (null before)
   float2* hr_grad = nullptr;       // [ld] the gradient of the phi_old being advanced
@@ -632,6 +632,7 @@ struct Solver {
   void set_scalar_solver(int field, const cfd_scalar_solver& c);
   void set_scalar_scheme(int field, const cfd_scalar_scheme& c);
   void scalar_scheme_stats(int field, cfd_scalar_scheme_stats* out) const;
+  ScalarSystem scalar_system() const;   // the assembled system of the field being advanced (sc_coef, sc_diag, sc_b)
   void scalar_krylov(ScalarField& f);   // the Krylov phase of one assembled field: f.phi becomes its frozen x
   void scalar_polish(int fi, ScalarField& f);   // the Jacobi loop from f.phi: sweeps, last_delta, converged
   void scalar_stats(int field, cfd_scalar_stats* out);

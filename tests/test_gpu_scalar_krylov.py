@@ -7,7 +7,8 @@ for.  Meshes and flows are those of tests/test_gpu_scalar.py:
   voronoi   5 to 9 slots per cell: the four-at-a-time slot loop runs 2 and 3 rounds
   fine      more than four 1,024-cell blocks and a ragged tail
   units4    bench_mesh(0.0066, 0): the reductions write units of 4 chunks, and
-            every iteration reduces four times
+            every iteration reduces four times; more than 256 sweep blocks, so
+            the fold of the sweep's delta strides
 
 Values fixed from runs of the restatement on the CPU (oracle fluxes, synthetic
 flow, dt = 0.2, inlet 0.25, tol 1e-6, max_sweeps 200, check_interval 4): every
@@ -77,6 +78,11 @@ def test_bit_exact_against_the_restatement(name, D):
     tests/scalar_krylov_ref.py; every case ends converged (module docstring)"""
     _check_shape(name)
     mesh, R = _mesh(name), _kref(name)
+    if name == "units4":
+        # the polish sweeps here are the only run of the block fold's strided
+        # path (more per-block values than its 256 threads): one value per
+        # 256-cell sweep block
+        assert (mesh.num_cells() + 255) // 256 > 256
     inlet = 0.25
     phi = _fields(mesh)[1].astype(F)
     s = _start(name, D, inlet, phi)
