@@ -9,4 +9,5 @@ from .mesh import (BackwardsStep, ChannelWithObstacle, CircleObstacle, Mesh,  # 
 from .solver import (GpuGroup, GpuSolver, adaptive_dt_rule, dist_plan, dist_unique_id,  # noqa: F401,E402
                      scalar_config_default, scalar_scheme_default, scalar_solver_default)
 from ._ffi import (Config, Constants, FlowDiag, ScalarConfig, ScalarParams, ScalarScheme,  # noqa: F401,E402
-                   ScalarSchemeStats, ScalarSolver, ScalarSolverStats, ScalarStats, build_id, default_config)
+                   ScalarSchemeStats, ScalarSolver, ScalarSolverStats, ScalarSource, ScalarStats, ScalarWall,
+                   ScalarWallFlux, build_id, default_config)

@@ -214,6 +214,24 @@ class ScalarSchemeStats(C.Structure):  # cfd_scalar_scheme_stats
         return {"scheme": self.scheme, "clamped_cells": self.clamped_cells}
 
 
+class ScalarWall(C.Structure):  # cfd_scalar_wall
+    _fields_ = [("kind", C.c_int32), ("value", C.c_float),
+                ("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double)]
+
+
+class ScalarSource(C.Structure):  # cfd_scalar_source
+    _fields_ = [("rate", C.c_float), ("reserved", C.c_int32),
+                ("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double)]
+
+
+class ScalarWallFlux(C.Structure):  # cfd_scalar_wall_flux
+    _fields_ = [("flux", C.c_double), ("area", C.c_double), ("phi_area", C.c_double),
+                ("faces", C.c_uint32), ("kind", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AmgLevel(C.Structure):  # cfd_amg_level
     _fields_ = [
         ("n", C.c_uint32), ("nc", C.c_uint32), ("nnz", C.c_uint64), ("r_nnz", C.c_uint64),
@@ -324,6 +342,7 @@ EXPORTED = [
     "cfd_scalar_advance", "cfd_scalar_stats_get",
     "cfd_scalar_solver_default", "cfd_set_scalar_solver", "cfd_scalar_solver_stats_get",
     "cfd_scalar_scheme_default", "cfd_set_scalar_scheme", "cfd_scalar_scheme_stats_get",
+    "cfd_set_scalar_wall", "cfd_set_scalar_source", "cfd_scalar_wall_flux_get",
 ]
 
 _lib = None

@@ -127,6 +127,9 @@ def _bind():
     L.cfd_scalar_scheme_default.restype = None
     L.cfd_set_scalar_scheme.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarScheme)]
     L.cfd_scalar_scheme_stats_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSchemeStats)]
+    L.cfd_set_scalar_wall.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarWall), u32p]
+    L.cfd_set_scalar_source.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSource), u32p]
+    L.cfd_scalar_wall_flux_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarWallFlux)]
     _bound = True
     return L
 
@@ -417,6 +420,38 @@ class GpuSolver:
     def scalar_scheme_stats(self, field) -> _ffi.ScalarSchemeStats:
         st = _ffi.ScalarSchemeStats()
         self._call("cfd_scalar_scheme_stats_get", int(field), C.byref(st))
+        return st
+
+    def set_scalar_wall(self, field, kind, value=0.0, box=(0.0, 0.0, -1.0, 0.0)) -> int:
+        """cfd_set_scalar_wall: the wall faces whose centre lies in the closed
+        ``box`` (x0, y0, x1, y1; x1 < x0: none) get ``kind`` "adiabatic" (0, the
+        default of every wall), "value" (1: phi = ``value`` on them, a heated
+        obstacle) or "flux" (2: ``value`` is the flux of density * phi per unit
+        area into the fluid).  One box and kind per field; takes effect at the
+        next advance_scalars().  Returns the faces in the box."""
+        kinds = {"adiabatic": 0, "value": 1, "flux": 2}
+        x0, y0, x1, y1 = (float(v) for v in box)
+        cfg = _ffi.ScalarWall(kinds[kind] if kind in kinds else int(kind), float(value), x0, y0, x1, y1)
+        n = C.c_uint32()
+        self._call("cfd_set_scalar_wall", int(field), C.byref(cfg), C.byref(n))
+        return int(n.value)
+
+    def set_scalar_source(self, field, rate, box=(0.0, 0.0, -1.0, 0.0)) -> int:
+        """cfd_set_scalar_source: ``rate`` (density * phi per unit volume and
+        time) in the cells whose centre lies in the closed ``box``; rate 0: none.
+        Returns the cells in the box."""
+        x0, y0, x1, y1 = (float(v) for v in box)
+        cfg = _ffi.ScalarSource(float(rate), 0, x0, y0, x1, y1)
+        n = C.c_uint32()
+        self._call("cfd_set_scalar_source", int(field), C.byref(cfg), C.byref(n))
+        return int(n.value)
+
+    def scalar_wall_flux(self, field) -> _ffi.ScalarWallFlux:
+        """cfd_scalar_wall_flux_get: the rate at which the selected wall faces
+        give density * phi to the fluid (current field), their area and the
+        area-weighted sum of the adjacent cell values."""
+        st = _ffi.ScalarWallFlux()
+        self._call("cfd_scalar_wall_flux_get", int(field), C.byref(st))
         return st
 
     # -- public status fields of the reference struct -------------------------

@@ -573,6 +573,47 @@ struct ScalarLimitedArgs {
   uint32_t* clamped;  // one word: += the cells whose t the clamp changed (the caller zeroes it)
 };
 void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s);
+// Wall conditions and sources of one field (include/cfd2_amd.h "Arithmetic of
+// wall conditions and sources" is the contract), a second kernel argument of
+// the boundary-condition forms only: the plain kernels above keep their
+// arguments.  sel[i]: bit k < 31 = slot k of cell i is a selected wall slot, bit
+// 31 = cell i is a source cell (the host builds it; a bit is set on wall slots
+// only).  Per selected wall slot, at the slot's place in the loop:
+//   kind 1   c_k = (density * D) * area / dist_e;  diag += c_k;  b += c_k * value
+//   kind 2   c_k = 0;  b += value * area
+// and after the slot loop b += vol_i * rate in a source cell.  Scheme 1: the
+// gradient's face value and the clamp's range take `value` on a kind-1 slot; the
+// inlet, kind-1 and kind-2 terms follow the clamp in one pass in slot order.
+struct ScalarBC {
+  const uint32_t* sel;  // [N]
+  int32_t kind;         // 0 (sources only), 1 fixed value, 2 fixed flux
+  float value;
+  float rate;           // 0: bit 31 of sel is clear everywhere
+};
+void launch_scalar_assemble_bc(const ScalarAssembleArgs& a, const ScalarBC& bc, hipStream_t s);
+void launch_scalar_grad_bc(const ScalarGradArgs& a, const ScalarBC& bc, hipStream_t s);  // kind 1 only
+void launch_scalar_assemble_limited_bc(const ScalarLimitedArgs& a, const ScalarBC& bc, hipStream_t s);
+// Read-only wall-flux diagnostic of one field: per cell, in f64 in slot order
+// over its selected slots, flux (kind 1: (double)c_k * ((double)value -
+// (double)phi_i), c_k the f32 above; kind 2: (double)value * (double)area), area
+// and area * phi_i; a cell without a selected slot reads none of its slot
+// arrays and adds +0.  Unit partials partial[f * np + unit], f = 0 flux, 1 area,
+// 2 phi_area, in the canonical tree (as launch_scalar_stats writes its sum).
+constexpr int kWallFluxSums = 3;
+struct ScalarWallFluxArgs {
+  uint32_t N;
+  const float* area;     // fs.area, [k*N + i]
+  const float* dist_e;   // fs.dist_e
+  const uint32_t* sel;   // [N]
+  const float* phi;      // [N]
+  float rd;              // density * D
+  int32_t kind;          // 1 or 2
+  float value;
+  uint32_t U;            // chunks per unit (RedGeom::U)
+  uint32_t np;           // unit partials per sum
+  double* partial;       // [kWallFluxSums * np]
+};
+void launch_scalar_wall_flux(const ScalarWallFluxArgs& a, hipStream_t s);
 // The assembled system as the solvers read it: the Jacobi row of cell i is
 //   J(phi)_i = (b_i + sum over internal slots k of c_k * phi[other_k]) / diag_i,
 // the sum left to right in slot order (boundary slots skipped), a true

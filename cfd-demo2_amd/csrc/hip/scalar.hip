@@ -8,6 +8,9 @@
 //   slots4        four slots of a cell from one slot-major array, the loads in
 //                 flight together (the gradient, the limited assembly, the row)
 //   scalar_coef   one slot's coefficient (both assemblies: the same bits)
+//   wall_slot     whether a boundary slot is a selected wall slot of ScalarBC
+//                 (the boundary-condition forms of the assemblies, the gradient
+//                 and the wall-flux sums)
 //   scalar_row    the Jacobi row sum of kernels.hpp ScalarSystem (the sweep
 //                 and the BiCGStab operator)
 //   reduce_dev.hpp: unit_partials (a block's sums), wave_max / block_of4_max
@@ -40,18 +43,33 @@ __device__ __forceinline__ float scalar_coef(float rd, float F, float area, floa
   const float cin = F < 0.0f ? -F : 0.0f;
   return cin + diff;
 }
+// A fixed-value wall slot's coefficient: the diffusive part alone (a wall
+// carries no flux), dist_e the distance the momentum wall diffusion uses
+__device__ __forceinline__ float scalar_wall_coef(float rd, float area, float dist_e) { return rd * area / dist_e; }
+// Boundary slot k of type bt is a selected wall slot of the cell's image word
+// (kernels.hpp ScalarBC: bits 0..30; the host refuses a selected face beyond)
+__device__ __forceinline__ bool wall_slot(uint32_t sel, uint32_t k, uint32_t bt) {
+  return bt == 3u && k < 31u && ((sel >> k) & 1u) != 0u;
+}
+constexpr uint32_t kSelWalls = 0x7FFFFFFFu;  // the wall-slot bits of an image word; bit 31: a source cell
 
 // Thread per cell (row_id: blocks remapped per XCD), every slot load one
-// coalesced wavefront access.
-__global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a) {
+// coalesced wavefront access.  BC: the form with wall conditions and sources
+// (kernels.hpp ScalarBC): one more coalesced load, the cell's image word, and a
+// bit test on wall slots only.
+template <bool BC>
+__device__ __forceinline__ void scalar_assemble(const ScalarAssembleArgs& a, const ScalarBC& bc) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
   const FaceSlots fs = a.fs;
-  const float a_t = a.vol[i] * a.density / a.dt;
+  const float vol = a.vol[i];
+  const float a_t = vol * a.density / a.dt;
   const float rd = a.density * a.diffusivity;
   float diag = a_t;
   float b = a_t * a.phi_old[i];
+  uint32_t sel = 0;
+  if constexpr (BC) sel = bc.sel[i];
   const uint32_t nf = fs.nface[i];
   for (uint32_t k = 0; k < nf; ++k) {
     const size_t e = (size_t)k * N + i;
@@ -59,19 +77,41 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a
     const bool internal = fs.other[e] != kNoCell;
     float c = 0.0f;  // wall: zero flux; outlet: zero gradient, flux >= 0 by construction
     if (internal || bt == 1u) c = scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]);  // flux_s: out of this cell
+    if constexpr (BC) {
+      if (!internal && wall_slot(sel, k, bt)) {
+        if (bc.kind == 1) {
+          c = scalar_wall_coef(rd, fs.area[e], fs.dist_e[e]);
+          b += c * bc.value;
+        } else {
+          b += bc.value * fs.area[e];
+        }
+      }
+    }
     a.coef[(size_t)k * a.ld + i] = c;
     diag += c;
     if (!internal && bt == 1u) b += c * a.inlet_value;
   }
+  if constexpr (BC) {
+    if (sel >> 31) b += vol * bc.rate;
+  }
   a.diag[i] = diag;
   a.b[i] = b;
+}
+__global__ void __launch_bounds__(kBlock) k_scalar_assemble(ScalarAssembleArgs a) {
+  scalar_assemble<false>(a, ScalarBC{});
+}
+__global__ void __launch_bounds__(kBlock) k_scalar_assemble_bc(ScalarAssembleArgs a, ScalarBC bc) {
+  scalar_assemble<true>(a, bc);
 }
 
 // ---- scheme 1, "limited linear" (kernels.hpp ScalarGradArgs / ScalarLimitedArgs) ----
 // The Green-Gauss gradient of phi_old, thread per cell: the face values of
 // prepare_cell's vfu branch (flux.hip), the slots four at a time (slots4, then
 // the four gathers in flight together), the sums in slot order; one 8-byte store.
-__global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
+// BC (a field with fixed-value walls): the face value of a selected wall slot
+// is the wall's value.
+template <bool BC>
+__device__ __forceinline__ void scalar_grad(const ScalarGradArgs& a, const ScalarBC& bc) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
@@ -79,6 +119,8 @@ __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
   const float pc = a.phi_old[i];
   const float vol = a.vol[i];
   float gx = 0.0f, gy = 0.0f;
+  uint32_t sel = 0;
+  if constexpr (BC) sel = bc.sel[i];
   const uint32_t nf = fs.nface[i];
   for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
     int32_t o[4];
@@ -100,11 +142,18 @@ __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
         vf = (mt[j] & kMetaDegen) == 0 ? lam[j] * pc + (1.0f - lam[j]) * po[j] : 0.5f * (pc + po[j]);
       else
         vf = (mt[j] & kMetaBtypeMask) == 1u ? a.inlet_value : pc;
+      if constexpr (BC) {
+        if (o[j] == kNoCell && wall_slot(sel, k0 + j, mt[j] & kMetaBtypeMask)) vf = bc.value;
+      }
       gx += vf * nx[j] * ar[j];
       gy += vf * ny[j] * ar[j];
     }
   }
   a.g[i] = make_float2(gx / vol, gy / vol);
+}
+__global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) { scalar_grad<false>(a, ScalarBC{}); }
+__global__ void __launch_bounds__(kBlock) k_scalar_grad_bc(ScalarGradArgs a, ScalarBC bc) {
+  scalar_grad<true>(a, bc);
 }
 
 // k_scalar_assemble with the limited right-hand side: the same coef and diag;
@@ -114,7 +163,12 @@ __global__ void __launch_bounds__(kBlock) k_scalar_grad(ScalarGradArgs a) {
 // remembered as a bit mask and their coefficients formed again afterwards
 // (the same expression, the same bits).  The block's clamped cells: a ballot
 // and a population count per wavefront, one atomic add per block.
-__global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimitedArgs q) {
+// BC (kernels.hpp ScalarBC): the selected wall slots are the image word's low
+// 31 bits, so they join the inlet mask's pass after the clamp -- one pass in
+// ascending slot order over both -- without a per-slot array; a fixed-value
+// slot also widens the clamp's range by its value.  The source comes last.
+template <bool BC>
+__device__ __forceinline__ void scalar_assemble_limited(const ScalarLimitedArgs& q, const ScalarBC& bc) {
   __shared__ uint32_t lcnt[kBlock / 64];
   const ScalarAssembleArgs& a = q.a;
   const uint32_t i = row_id();
@@ -128,6 +182,8 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
     const float2 gc = q.g[i];
     float diag = a_t, corr = 0.0f, mn = pc, mx = pc;
     uint32_t inlets = 0;  // bit k: slot k is an inlet slot (the host refuses wf > 32)
+    uint32_t sel = 0;
+    if constexpr (BC) sel = bc.sel[i];
     const uint32_t nf = fs.nface[i];
     for (uint32_t k0 = 0; k0 < nf; k0 += 4) {
       int32_t o[4];
@@ -153,7 +209,14 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
         if (k >= nf) continue;
         const uint32_t bt = mt[j] & kMetaBtypeMask;
         const bool internal = o[j] != kNoCell;
-        const float c = internal || bt == 1u ? scalar_coef(rd, F[j], ar[j], de[j]) : 0.0f;
+        float c = internal || bt == 1u ? scalar_coef(rd, F[j], ar[j], de[j]) : 0.0f;
+        if constexpr (BC) {
+          if (!internal && bc.kind == 1 && wall_slot(sel, k, bt)) {
+            c = scalar_wall_coef(rd, ar[j], de[j]);
+            mn = bc.value < mn ? bc.value : mn;
+            mx = bc.value > mx ? bc.value : mx;
+          }
+        }
         a.coef[(size_t)k * a.ld + i] = c;
         diag += c;
         if (internal) {
@@ -186,11 +249,27 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
     clamped = t < lo || t > hi;
     t = t < lo ? lo : (t > hi ? hi : t);
     float b = t;
-    while (inlets) {
-      const uint32_t k = (uint32_t)__ffs((int)inlets) - 1u;
-      inlets &= inlets - 1u;
-      const size_t e = (size_t)k * N + i;
-      b += scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]) * a.inlet_value;
+    if constexpr (!BC) {
+      while (inlets) {
+        const uint32_t k = (uint32_t)__ffs((int)inlets) - 1u;
+        inlets &= inlets - 1u;
+        const size_t e = (size_t)k * N + i;
+        b += scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]) * a.inlet_value;
+      }
+    } else {
+      uint32_t late = inlets | (sel & kSelWalls);  // an image bit is set on wall slots only
+      while (late) {
+        const uint32_t k = (uint32_t)__ffs((int)late) - 1u;
+        late &= late - 1u;
+        const size_t e = (size_t)k * N + i;
+        if ((inlets >> k) & 1u)
+          b += scalar_coef(rd, a.flux_s[e], fs.area[e], fs.dist_e[e]) * a.inlet_value;
+        else if (bc.kind == 1)
+          b += scalar_wall_coef(rd, fs.area[e], fs.dist_e[e]) * bc.value;
+        else
+          b += bc.value * fs.area[e];
+      }
+      if (sel >> 31) b += a.vol[i] * bc.rate;
     }
     a.b[i] = b;
   }
@@ -201,6 +280,12 @@ __global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimite
     const uint32_t n = (lcnt[0] + lcnt[1]) + (lcnt[2] + lcnt[3]);
     if (n) atomicAdd(q.clamped, n);
   }
+}
+__global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited(ScalarLimitedArgs q) {
+  scalar_assemble_limited<false>(q, ScalarBC{});
+}
+__global__ void __launch_bounds__(kBlock) k_scalar_assemble_limited_bc(ScalarLimitedArgs q, ScalarBC bc) {
+  scalar_assemble_limited<true>(q, bc);
 }
 
 // The Jacobi row sum of cell i (kernels.hpp ScalarSystem) over the vector `in`,
@@ -285,6 +370,47 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
     a.blockmm[2 * (size_t)lb] = block_of4_min(lmm[0]);
     a.blockmm[2 * (size_t)lb + 1] = block_of4_max(lmm[1]);
   }
+}
+
+// The wall-flux sums (kernels.hpp ScalarWallFluxArgs), the shape of
+// k_scalar_stats: a cell with a selected slot walks the set bits of its image
+// word in ascending order, every other cell loads that word alone.  Read-only.
+__global__ void __launch_bounds__(kBlock) k_scalar_wall_flux(ScalarWallFluxArgs a) {
+  __shared__ double lsum[kWallFluxSums][4][4];  // [sum][chunk q][quarter w]
+  const uint32_t N = a.N;
+  const uint32_t lb = xcd_block();
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
+    double t[kWallFluxSums] = {0.0, 0.0, 0.0};
+    if (ci < N) {
+      const uint32_t i = (uint32_t)ci;
+      uint32_t walls = a.sel[i] & kSelWalls;
+      if (walls) {
+        const double ph = (double)a.phi[i];
+        while (walls) {
+          const uint32_t k = (uint32_t)__ffs((int)walls) - 1u;
+          walls &= walls - 1u;
+          const size_t e = (size_t)k * N + i;
+          const float area = a.area[e];
+          if (a.kind == 1)
+            t[0] += (double)scalar_wall_coef(a.rd, area, a.dist_e[e]) * ((double)a.value - ph);
+          else
+            t[0] += (double)a.value * (double)area;
+          t[1] += (double)area;
+          t[2] += (double)area * ph;
+        }
+      }
+    }
+#pragma unroll
+    for (int f = 0; f < kWallFluxSums; ++f) {
+      const double r = wave_tree(t[f]);
+      if (lane == 0) lsum[f][q][w] = r;
+    }
+  }
+  __syncthreads();
+  const uint32_t UB = 4 / a.U, f = threadIdx.x / UB;  // thread f UB + u: unit u of sum f
+  if (f < kWallFluxSums) unit_partials(lsum[f], a.U, a.np, N, lb, a.partial + (size_t)f * a.np, threadIdx.x % UB);
 }
 
 // ---- BiCGStab on the Jacobi-scaled system (kernels.hpp ScalarKrylovArgs) ----
@@ -564,6 +690,26 @@ void launch_scalar_grad(const ScalarGradArgs& a, hipStream_t s) {
 void launch_scalar_assemble_limited(const ScalarLimitedArgs& a, hipStream_t s) {
   if (!a.a.N) return;
   hipLaunchKernelGGL(k_scalar_assemble_limited, dim3(grid_for(a.a.N)), dim3(kBlock), 0, s, a);
+}
+
+void launch_scalar_assemble_bc(const ScalarAssembleArgs& a, const ScalarBC& bc, hipStream_t s) {
+  if (!a.N) return;
+  hipLaunchKernelGGL(k_scalar_assemble_bc, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, bc);
+}
+
+void launch_scalar_grad_bc(const ScalarGradArgs& a, const ScalarBC& bc, hipStream_t s) {
+  if (!a.N) return;
+  hipLaunchKernelGGL(k_scalar_grad_bc, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, bc);
+}
+
+void launch_scalar_assemble_limited_bc(const ScalarLimitedArgs& a, const ScalarBC& bc, hipStream_t s) {
+  if (!a.a.N) return;
+  hipLaunchKernelGGL(k_scalar_assemble_limited_bc, dim3(grid_for(a.a.N)), dim3(kBlock), 0, s, a, bc);
+}
+
+void launch_scalar_wall_flux(const ScalarWallFluxArgs& a, hipStream_t s) {
+  const uint32_t nb = red_blocks(a.N);
+  if (nb) hipLaunchKernelGGL(k_scalar_wall_flux, dim3(nb), dim3(kBlock), 0, s, a);
 }
 
 void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s) {

@@ -627,6 +627,27 @@ cfd_status cfd_scalar_scheme_stats_get(cfd_solver* s, int32_t field, cfd_scalar_
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
   return guard([&] { s->s->scalar_scheme_stats(field, out); });
 }
+cfd_status cfd_set_scalar_wall(cfd_solver* s, int32_t field, const cfd_scalar_wall* cfg, uint32_t* faces) {
+  CHECK_S(s);
+  if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar wall config");
+  return guard([&] {
+    const uint32_t n = s->s->set_scalar_wall(field, *cfg);
+    if (faces) *faces = n;
+  });
+}
+cfd_status cfd_set_scalar_source(cfd_solver* s, int32_t field, const cfd_scalar_source* cfg, uint32_t* cells) {
+  CHECK_S(s);
+  if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar source config");
+  return guard([&] {
+    const uint32_t n = s->s->set_scalar_source(field, *cfg);
+    if (cells) *cells = n;
+  });
+}
+cfd_status cfd_scalar_wall_flux_get(cfd_solver* s, int32_t field, cfd_scalar_wall_flux* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->scalar_wall_flux(field, out); });
+}
 
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {

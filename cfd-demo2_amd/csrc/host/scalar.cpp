@@ -4,7 +4,9 @@
 // the host reading the last sweep's delta after each batch.  A field on method
 // 1 runs BiCGStab between the two and starts the sweeps from its answer.  A
 // field on scheme 1 takes its right-hand side from the gradient pass and the
-// limited assembly instead; everything after the assembly is the same.
+// limited assembly instead; everything after the assembly is the same.  A field
+// with a wall condition or a source (kernels.hpp ScalarBC) runs the boundary-
+// condition forms of those passes; a field without runs the plain ones.
 #include <cmath>
 #include <cstring>
 
@@ -35,6 +37,7 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   kr_state = nullptr;
   hr_grad = nullptr;
   hr_count = nullptr;
+  wf_partial = wf_res = nullptr;
   for (ScalarField& f : sc_field) f = ScalarField{};
   if (count == 0) return;
   const size_t ld = topo.ld;
@@ -110,17 +113,28 @@ void Solver::scalar_advance(float dt) {
     A.b = sc_b;
     f.scheme_used = f.scheme;
     f.clamped = 0;
+    const bool bc = f.wall_on() || f.source_on();
+    const ScalarBC B{f.sel, f.wall_on() ? f.wall.kind : 0, f.wall.value, f.source_on() ? f.source.rate : 0.0f};
     if (f.scheme == 1) {
       // the gradient of phi_old first, every cell before any is read; then the
       // assembly with the limited right-hand side.  The count lands in
       // f.clamped with the first read of the solve below.
-      launch_scalar_grad(ScalarGradArgs(A, hr_grad), stream);
+      if (B.kind == 1)
+        launch_scalar_grad_bc(ScalarGradArgs(A, hr_grad), B, stream);
+      else
+        launch_scalar_grad(ScalarGradArgs(A, hr_grad), stream);
       CFD_HIP(hipMemsetAsync(hr_count + fi, 0, sizeof(uint32_t), stream));
-      launch_scalar_assemble_limited(ScalarLimitedArgs{A, hr_grad, hr_count + fi}, stream);
+      if (bc)
+        launch_scalar_assemble_limited_bc(ScalarLimitedArgs{A, hr_grad, hr_count + fi}, B, stream);
+      else
+        launch_scalar_assemble_limited(ScalarLimitedArgs{A, hr_grad, hr_count + fi}, stream);
       check_launch("scalar limited assemble");
       CFD_HIP(hipMemcpyAsync(&f.clamped, hr_count + fi, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     } else {
-      launch_scalar_assemble(A, stream);
+      if (bc)
+        launch_scalar_assemble_bc(A, B, stream);
+      else
+        launch_scalar_assemble(A, stream);
       check_launch("scalar assemble");
     }
     f.sweeps = 0;
@@ -247,6 +261,104 @@ void Solver::scalar_scheme_stats(int field, cfd_scalar_scheme_stats* out) const 
   std::memset(out, 0, sizeof(*out));
   out->scheme = sc_field[field].scheme_used;
   out->clamped_cells = sc_field[field].clamped;
+}
+
+// The selection image of one field from its wall box and its source box: bit k
+// < 31 of word i = slot k of cell i is a selected wall face (kind 1 or 2 only),
+// bit 31 = cell i is a source cell (rate != 0 only).  Allocated at the first
+// selection that sets a bit; a field without one keeps the plain kernels.
+void Solver::scalar_select(ScalarField& f) {
+  if (!f.wall_on() && !f.source_on()) return;
+  std::vector<uint32_t> img(N, 0u);
+  if (f.wall_on()) {
+    const cfd_scalar_wall& w = f.wall;
+    for (const WallFace& wfc : wall_faces)
+      if (wfc.cx >= w.x0 && wfc.cx <= w.x1 && wfc.cy >= w.y0 && wfc.cy <= w.y1) img[wfc.cell] |= 1u << wfc.slot;
+  }
+  if (f.source_on()) {
+    const cfd_scalar_source& q = f.source;
+    for (uint32_t i = 0; i < N; ++i)
+      if (cell_cx[i] >= q.x0 && cell_cx[i] <= q.x1 && cell_cy[i] >= q.y0 && cell_cy[i] <= q.y1) img[i] |= 1u << 31;
+  }
+  CFD_HIP(hipSetDevice(device));
+  if (!f.sel) f.sel = sc_arena.alloc<uint32_t>(N);
+  CFD_HIP(hipMemcpyAsync(f.sel, img.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  sync();
+}
+
+uint32_t Solver::set_scalar_wall(int field, const cfd_scalar_wall& c) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar wall on a distributed handle");
+  scalar_check(field);
+  if (c.kind < 0 || c.kind > 2)
+    throw std::invalid_argument("scalar wall: kind must be 0 (adiabatic), 1 (fixed value) or 2 (fixed flux)");
+  if (!std::isfinite(c.value)) throw std::invalid_argument("scalar wall: value must be finite");
+  uint32_t count = 0;
+  if (!(c.x1 < c.x0))
+    for (const WallFace& wfc : wall_faces) {
+      if (!(wfc.cx >= c.x0 && wfc.cx <= c.x1 && wfc.cy >= c.y0 && wfc.cy <= c.y1)) continue;
+      if (c.kind != 0 && wfc.slot >= 31)
+        throw std::invalid_argument("scalar wall keeps a cell's selected wall slots in 31 bits: wall face at slot 31 or "
+                                    "above of its cell");
+      ++count;
+    }
+  ScalarField& f = sc_field[field];
+  f.wall = c;
+  f.wall_n = count;
+  scalar_select(f);
+  return count;
+}
+
+uint32_t Solver::set_scalar_source(int field, const cfd_scalar_source& c) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar source on a distributed handle");
+  scalar_check(field);
+  if (!std::isfinite(c.rate)) throw std::invalid_argument("scalar source: rate must be finite");
+  uint32_t count = 0;
+  if (!(c.x1 < c.x0))
+    for (uint32_t i = 0; i < N; ++i)
+      if (cell_cx[i] >= c.x0 && cell_cx[i] <= c.x1 && cell_cy[i] >= c.y0 && cell_cy[i] <= c.y1) ++count;
+  ScalarField& f = sc_field[field];
+  f.source = c;
+  f.source_n = count;
+  scalar_select(f);
+  return count;
+}
+
+// Read-only on the current field, with the current density and diffusivity; a
+// field without selected faces launches nothing.
+void Solver::scalar_wall_flux(int field, cfd_scalar_wall_flux* out) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no scalar wall flux on a distributed handle");
+  scalar_check(field);
+  const ScalarField& f = sc_field[field];
+  std::memset(out, 0, sizeof(*out));
+  out->faces = f.wall_n;
+  out->kind = f.wall.kind;
+  if (!f.wall_on()) return;
+  CFD_HIP(hipSetDevice(device));
+  if (!wf_partial) {
+    wf_partial = sc_arena.alloc<double>((size_t)kWallFluxSums * pstride);
+    wf_res = sc_arena.alloc<double>(kWallFluxSums);
+  }
+  ScalarWallFluxArgs a{};
+  a.N = N;
+  a.area = fs.area;
+  a.dist_e = fs.dist_e;
+  a.sel = f.sel;
+  a.phi = f.phi;
+  a.rd = constants.density * f.par.diffusivity;
+  a.kind = f.wall.kind;
+  a.value = f.wall.value;
+  a.U = red.U;
+  a.np = pstride;
+  a.partial = wf_partial;
+  launch_scalar_wall_flux(a, stream);
+  launch_evolution_final(combine(wf_partial, kWallFluxSums), wf_res, stream);
+  check_launch("scalar wall flux");
+  double h[kWallFluxSums];
+  CFD_HIP(hipMemcpyAsync(h, wf_res, sizeof(h), hipMemcpyDeviceToHost, stream));
+  sync();
+  out->flux = h[0];
+  out->area = h[1];
+  out->phi_area = h[2];
 }
 
 void Solver::scalar_stats(int field, cfd_scalar_stats* out) {

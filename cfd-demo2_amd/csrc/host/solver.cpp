@@ -62,6 +62,10 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
       if (mesh.face_neighbor[f] == UINT32_MAX && (mesh.face_boundary[f] & 3u) == 3u)
         wall_faces.push_back({mesh.face_cx[f], mesh.face_cy[f], i, k - mesh.cell_face_offsets[i]});
     }
+  if (R == 1) {  // passive scalars (one GPU only): the source box tests the f64 centres
+    cell_cx.assign(mesh.cell_cx, mesh.cell_cx + NG);
+    cell_cy.assign(mesh.cell_cy, mesh.cell_cy + NG);
+  }
   red = red_geom(NG);
   if (red.nseg > kRedMaxSegments)
     throw std::invalid_argument("mesh too large for the reduction tree (at most 268 M cells)");

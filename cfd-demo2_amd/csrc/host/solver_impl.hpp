@@ -602,6 +602,14 @@ struct Solver {
     int32_t scheme = 0;                      // cfd_scalar_scheme.scheme, for the next advance
     int32_t scheme_used = 0;                 // of the last advance
     uint32_t clamped = 0;                    // of the last advance (copied from hr_count during it)
+    // wall condition and source (cfd_set_scalar_wall / cfd_set_scalar_source), for the next advance
+    cfd_scalar_wall wall{};                  // kind 0: every wall adiabatic
+    cfd_scalar_source source{};              // rate 0: none
+    uint32_t wall_n = 0;                     // wall faces in wall's box
+    uint32_t source_n = 0;                   // cells in source's box
+    uint32_t* sel = nullptr;                 // [N] the selection image (kernels.hpp ScalarBC), null before the first non-trivial selection
+    bool wall_on() const { return wall.kind != 0 && wall_n != 0; }
+    bool source_on() const { return source.rate != 0.0f && source_n != 0; }
   };
   DeviceArena sc_arena;
   int sc_count = 0;
@@ -623,6 +631,11 @@ struct Solver {
   // set_scalar_scheme that selects it (null before)
   float2* hr_grad = nullptr;       // [ld] the gradient of the phi_old being advanced
   uint32_t* hr_count = nullptr;    // [4] clamped cells of each field's last scheme-1 assembly
+  // Wall-flux work space, allocated in sc_arena by the first scalar_wall_flux
+  // that has faces to sum over (null before)
+  double* wf_partial = nullptr;    // [kWallFluxSums * pstride] unit partials
+  double* wf_res = nullptr;        // [kWallFluxSums] flux, area, phi_area
+  std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: the source box)
   float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
   void scalars_enable(int count, const cfd_scalar_config& c);
   void scalar_check(int field) const;  // throws std::invalid_argument: not enabled / bad index
@@ -636,6 +649,10 @@ struct Solver {
   void scalar_krylov(ScalarField& f);   // the Krylov phase of one assembled field: f.phi becomes its frozen x
   void scalar_polish(int fi, ScalarField& f);   // the Jacobi loop from f.phi: sweeps, last_delta, converged
   void scalar_stats(int field, cfd_scalar_stats* out);
+  uint32_t set_scalar_wall(int field, const cfd_scalar_wall& c);      // returns the faces selected
+  uint32_t set_scalar_source(int field, const cfd_scalar_source& c);  // returns the cells selected
+  void scalar_select(ScalarField& f);   // f.sel from f.wall and f.source (allocates and uploads it when either is on)
+  void scalar_wall_flux(int field, cfd_scalar_wall_flux* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

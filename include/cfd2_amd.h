@@ -790,6 +790,100 @@ void cfd_scalar_scheme_default(cfd_scalar_scheme* cfg); /* scheme 0; null ignore
 cfd_status cfd_set_scalar_scheme(cfd_solver* s, int32_t field, const cfd_scalar_scheme* cfg);
 cfd_status cfd_scalar_scheme_stats_get(cfd_solver* s, int32_t field, cfd_scalar_scheme_stats* out);
 
+/* Wall conditions, sources and the wall-flux diagnostic of one scalar field.
+ * By default every wall face is adiabatic (c_k = 0 above) and there is no
+ * source, so a temperature can only enter through the inlet.  Per field, one
+ * box of wall faces can carry a fixed value (a heated obstacle) or a fixed
+ * flux, one box of cells a uniform source, and the rate at which the selected
+ * faces give density * phi to the fluid can be read: the scalar counterpart of
+ * cfd_flow_diag's wall force.  Everything is per field and opt-in: a field with
+ * kind 0 and rate 0 launches the kernels above with the same arguments and
+ * produces the same bits, a handle that never selects anything allocates
+ * nothing new on the device, and cfd_step launches none of it in any case.
+ * (On the host every one-GPU handle keeps the mesh view's f64 cell centres
+ * from its creation, 16 bytes per cell, for the source box: the view itself
+ * is not kept.)  The first
+ * selection of a field that marks a face or a cell allocates its selection
+ * image (one 32-bit word per cell), the first cfd_scalar_wall_flux_get with
+ * faces to sum a few unit partials; cfd_scalars_enable frees both and resets
+ * every field to kind 0 and rate 0.  One wall box and kind and one source box
+ * per field, constant in time.  One GPU only, as the scalars are; checkpoints
+ * neither store nor touch any of it.
+ *
+ * Arithmetic of wall conditions and sources.  All f32, one rounding per
+ * operation (nothing fused), every sum left to right in face-slot order; rd =
+ * density * D_f, A_k the face area, d_k the distance from the cell centre to
+ * the face centre, the one the momentum wall diffusion uses.  Only wall faces
+ * (boundary type 3) can be selected; an unselected wall stays adiabatic.
+ *   kind 1     (fixed value) on a selected slot c_k = rd * A_k / d_k -- no
+ *              convective part, a wall carries no flux -- and, at the slot's
+ *              place in the loop, diag += c_k and b += c_k * value, as an inlet
+ *              slot does with inlet_value.  The Jacobi row skips boundary slots
+ *              as before.
+ *   kind 2     (fixed flux) on a selected slot c_k = 0 and, at the slot's place,
+ *              b += value * A_k: value is the flux of density * phi per unit
+ *              area INTO the fluid.
+ *   source     in a selected cell, after the slot loop, b += vol_i * rate: rate
+ *              is density * phi per unit volume and time.
+ *   scheme 1   gradient: the face value of a selected kind-1 slot is value
+ *              (every other wall slot: phi_i as before).  clamp: m_i and M_i also
+ *              take v = value on a selected kind-1 slot, at the slot's place, as
+ *              they take inlet_value on an inlet slot.  The clamp applies to
+ *              a_t * phi_i - corr_i as before; b_i = t, then one pass in
+ *              ascending slot order over the inlet slots and the selected wall
+ *              slots adds c_k * inlet_value (inlet), c_k * value (kind 1, c_k
+ *              formed again by the same expression) or value * A_k (kind 2);
+ *              the source term comes last.
+ * The bound.  With kind 1 alone every Jacobi iterate is still a convex
+ * combination: the weights gain c_k / diag_i on `value`.  A dye in [0, 1] with
+ * value in [0, 1] keeps its bound with scheme 0's rounding allowance under
+ * schemes 0 and 1, and method 1 keeps its own tol * max_i(diag_i / a_t,i).
+ * Kind 2 and sources add to b without a matching weight: they are outside the
+ * bound by construction (a heated wall heats).
+ *   wall flux  per cell, in f64, in slot order over its selected slots, from +0:
+ *                kind 1   flux += (double)c_k * ((double)value - (double)phi_i),
+ *                         c_k the f32 coefficient above
+ *                kind 2   flux += (double)value * (double)A_k
+ *                area += (double)A_k;  phi_area += (double)A_k * (double)phi_i
+ *              and the three per-cell terms (+0 in a cell without a selected
+ *              slot) summed over the cells in the canonical order, the tree of
+ *              cfd_scalar_stats.integral.  phi is the current field and density
+ *              and D_f the current ones: right after an advance, flux is the
+ *              implicit wall term of that advance, so that
+ *                (density / dt) (I_new - I_old) = inlet + outlet + defect - clamp
+ *                                                 + flux + rate * (volume of the source cells)
+ *              closes to the rounding of the rows.                            */
+typedef struct cfd_scalar_wall {
+  int32_t kind;            /* 0 adiabatic (the default), 1 fixed value, 2 fixed flux */
+  float value;             /* kind 1: phi on the selected faces; kind 2: the flux into the fluid */
+  double x0, y0, x1, y1;   /* closed box over the f64 wall-face centres, cfd_set_force_region's rule; x1 < x0: none */
+} cfd_scalar_wall;
+typedef struct cfd_scalar_source {
+  float rate;              /* density * phi per unit volume and time; 0: none */
+  int32_t reserved;
+  double x0, y0, x1, y1;   /* closed box over the f64 cell centres; x1 < x0: none */
+} cfd_scalar_source;
+typedef struct cfd_scalar_wall_flux {
+  double flux;             /* density * phi per unit time entering the fluid through the selected faces */
+  double area;             /* sum of their areas */
+  double phi_area;         /* sum of A_k * phi_i over them (mean adjacent value = phi_area / area) */
+  uint32_t faces;          /* wall faces in the field's box */
+  int32_t kind;            /* the field's wall kind */
+} cfd_scalar_wall_flux;
+/* Both setters take effect at the next cfd_scalar_advance; *count (optional)
+ * receives the wall faces / cells in the box.  Kind 0, a box without a wall
+ * face, rate 0 or a box without a cell put the field back on the plain
+ * kernels.  CFD_ERR_INVALID: scalars not enabled, a bad field index, a kind
+ * outside 0..2, a value or rate that is not finite, a distributed handle, or
+ * (kind 1 or 2) a selected wall face at slot 31 or above of its cell: the
+ * selection keeps a cell's slots in 31 bits, as scheme 1 keeps 32.  A refused
+ * call changes nothing.                                                      */
+cfd_status cfd_set_scalar_wall(cfd_solver* s, int32_t field, const cfd_scalar_wall* cfg, uint32_t* faces);
+cfd_status cfd_set_scalar_source(cfd_solver* s, int32_t field, const cfd_scalar_source* cfg, uint32_t* cells);
+/* The wall-flux sums of the field as it stands.  Kind 0 or no selected face:
+ * zeros (faces and kind filled in), nothing launched.                        */
+cfd_status cfd_scalar_wall_flux_get(cfd_solver* s, int32_t field, cfd_scalar_wall_flux* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,17 @@ profile and exactly 4 sweeps long, medians of 20 fenced calls, scheme 0 timed
 before and after scheme 1; beside it the layout bytes of the two new passes
 less those of the assembly they replace, at the sweep kernel's rate of the
 same session.  Writes profiles/r10/scalar_hr.json.
+
+--wall: instead, the extra time of the boundary-condition forms of the
+assemblies (set_scalar_wall: the obstacle's faces at a fixed value) over their
+plain siblings under scheme 0 and under scheme 1, on one handle in one session
+as --scheme times its pair: the plain advance before and after the one with the
+wall; the median of 20 fenced scalar_wall_flux() calls (k_scalar_wall_flux, the
+one-block finish and a 24-byte read: a whole host call, not the kernel's own
+time, which a kernel trace of this run gives); the extra layout bytes (4 B per
+cell per pass that reads the selection image) over the extra times, left null
+where the extra is below the spread of the two plain runs that bracket it,
+beside the sweep kernel's rate of the same session.  Writes profiles/r12/scalar_bc.json.
 """
 from __future__ import annotations
 
@@ -166,6 +177,61 @@ def scheme_row(s, mesh, name, np):
                 layout_bytes=lb)
 
 
+OBSTACLE_BOX = (0.85, 0.36, 1.15, 0.66)  # around bench_channel's obstacle ((1.0, 0.51), r = 0.1), off the channel walls
+
+
+def wall_row(s, mesh, name, np):
+    """scheme_row's protocol (one batch of 4 sweeps from the same step profile
+    per call, medians of 20 fenced calls) for a field with and without a
+    fixed-value wall on the obstacle, under scheme 0 and scheme 1."""
+    x = mesh.arrays()["cell_cx"]
+    dye = np.where(x < 0.5, 1.0, 0.0)
+    n = float(mesh.num_cells())
+
+    def run(scheme, wall, reps=20, **cfg):
+        s.enable_scalars(1, **cfg)
+        s.set_scalar_params(0, DIFFUSIVITY, 1.0)
+        s.set_scalar_scheme(0, scheme)
+        faces = s.set_scalar_wall(0, "value", 1.0, OBSTACLE_BOX) if wall else 0
+        ts = []
+        for _ in range(reps + 1):  # the first call is the warm-up
+            s.set_scalar(0, dye)
+            s.synchronize()
+            t0 = time.perf_counter()
+            s.advance_scalars()
+            s.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts[1:]), faces
+
+    one = dict(max_sweeps=4, check_interval=4)
+    out = dict(config=name, cells=mesh.num_cells(), dt=1e-3, diffusivity=DIFFUSIVITY, sweeps_per_call=4)
+    plain = {}
+    for scheme, passes in (("upwind", 1), ("vanleer", 2)):
+        p0, _ = run(scheme, False, **one)
+        w, faces = run(scheme, True, **one)
+        p1, _ = run(scheme, False, **one)
+        plain[scheme] = 0.5 * (p0 + p1)
+        extra, spread = w - plain[scheme], abs(p1 - p0)
+        out[scheme] = dict(plain_ms=1e3 * p0, wall_ms=1e3 * w, plain_again_ms=1e3 * p1, extra_us=1e6 * extra,
+                           plain_spread_us=1e6 * spread, extra_layout_bytes=4.0 * n * passes,
+                           extra_gbs=4.0 * n * passes / extra / 1e9 if extra > spread else None)
+        out["faces"] = faces
+    # the wall-flux call on the field the last wall run left
+    run("upwind", True, reps=1, **one)
+    ts = []
+    for _ in range(21):
+        s.synchronize()
+        t0 = time.perf_counter()
+        wf = s.scalar_wall_flux(0)
+        ts.append(time.perf_counter() - t0)
+    f = statistics.median(ts[1:])
+    t64, _ = run("upwind", False, reps=10, max_sweeps=64, check_interval=64)
+    sweep = (t64 - plain["upwind"]) / 60.0
+    sb = sweep_layout_bytes(mesh)
+    out.update(wall_flux_call_us=1e6 * f, wall_flux_layout_bytes=4.0 * n, wall_flux=wf.as_dict(), sweep_us=1e6 * sweep, sweep_layout_bytes=sb, sweep_gbs=sb / sweep / 1e9)
+    return out
+
+
 def fenced(solver, fn, reps=20):
     ts, sweeps = [], []
     for _ in range(reps):
@@ -185,11 +251,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--krylov", action="store_true", help="Jacobi against BiCGStab (profiles/r09/scalar_krylov.json)")
     ap.add_argument("--scheme", action="store_true", help="scheme 1 against scheme 0 (profiles/r10/scalar_hr.json)")
+    ap.add_argument("--wall", action="store_true", help="the wall-condition forms against the plain ones (profiles/r12/scalar_bc.json)")
     args = ap.parse_args()
-    if args.krylov and args.scheme:
-        ap.error("--krylov and --scheme are separate runs")
+    if args.krylov + args.scheme + args.wall > 1:
+        ap.error("--krylov, --scheme and --wall are separate runs")
     if args.out is None:
-        where = ("r10", "scalar_hr.json") if args.scheme else ("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")
+        where = ("r12", "scalar_bc.json") if args.wall else ("r10", "scalar_hr.json") if args.scheme else ("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")
         args.out = os.path.join(ROOT, "profiles", *where)
     import numpy as np
     from cfd2_amd import GpuSolver, build_id, default_config
@@ -212,10 +279,10 @@ def main():
         s.set_alpha_p(0.3)
         s.set_precond_type(1)
         s.initialize_history()
-        if args.scheme:
+        if args.scheme or args.wall:
             s.step()
             s.step()
-            row = scheme_row(s, mesh, name, np)
+            row = (wall_row if args.wall else scheme_row)(s, mesh, name, np)
             row["build"] = build_id()
             print(json.dumps(row), flush=True)
             rows.append(row)
@@ -269,6 +336,19 @@ def main():
         s.close()
         del mesh
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.wall:
+        with open(args.out, "w") as fh:
+            json.dump(dict(what="one field, dt 1e-3, D 1e-4, one handle after 2 steps, every advance from the same step "
+                                "profile and one batch of 4 sweeps long (tools/scalar_cost.py --wall): medians of 20 fenced "
+                                "advance_scalars() calls without a wall condition, with the obstacle's faces at a fixed "
+                                "value, and without again, under scheme 0 (upwind) and scheme 1 (vanleer); extra = with - "
+                                "the mean of the two without, extra_gbs null where it is not above their spread; "
+                                "wall_flux_call_us = the median of 20 fenced scalar_wall_flux() calls (two launches, a "
+                                "24-byte read, a synchronisation: not the kernel's time); one sweep = (64 sweeps - 4 sweeps) / 60; extra layout bytes = 4 B per cell per "
+                                "pass that reads the selection image",
+                           rows=rows), fh, indent=1)
+            fh.write("\n")
+        return
     if args.scheme:
         with open(args.out, "w") as fh:
             json.dump(dict(what="one field, dt 1e-3, D 1e-4, one handle after 2 steps, every advance from the same step "
