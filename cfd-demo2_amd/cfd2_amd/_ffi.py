@@ -232,6 +232,15 @@ class ScalarWallFlux(C.Structure):  # cfd_scalar_wall_flux
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Buoyancy(C.Structure):  # cfd_buoyancy
+    _fields_ = [("gx", C.c_float), ("gy", C.c_float), ("fields", C.c_int32), ("active", C.c_int32),
+                ("beta", C.c_float * 4), ("ref", C.c_float * 4)]
+
+
+class BuoyancyForce(C.Structure):  # cfd_buoyancy_force
+    _fields_ = [("force", C.c_double * 2), ("fields", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class AmgLevel(C.Structure):  # cfd_amg_level
     _fields_ = [
         ("n", C.c_uint32), ("nc", C.c_uint32), ("nnz", C.c_uint64), ("r_nnz", C.c_uint64),
@@ -343,6 +352,7 @@ EXPORTED = [
     "cfd_scalar_solver_default", "cfd_set_scalar_solver", "cfd_scalar_solver_stats_get",
     "cfd_scalar_scheme_default", "cfd_set_scalar_scheme", "cfd_scalar_scheme_stats_get",
     "cfd_set_scalar_wall", "cfd_set_scalar_source", "cfd_scalar_wall_flux_get",
+    "cfd_set_scalar_buoyancy", "cfd_set_gravity", "cfd_buoyancy_get", "cfd_buoyancy_force_get",
 ]
 
 _lib = None

@@ -5,6 +5,7 @@ There is no CPU fallback: constructing a solver without a GPU raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -14,6 +15,9 @@ from . import _ffi
 
 _vp = C.c_void_p
 _bound = False
+
+# GpuSolver.buoyancy_force(): the two force components and the number of driving fields
+BuoyancyForce = collections.namedtuple("BuoyancyForce", "fx fy fields")
 
 
 # cfd_exchange_fn / cfd_allgather_fn (include/cfd2_amd.h)
@@ -130,6 +134,10 @@ def _bind():
     L.cfd_set_scalar_wall.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarWall), u32p]
     L.cfd_set_scalar_source.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarSource), u32p]
     L.cfd_scalar_wall_flux_get.argtypes = [_vp, C.c_int32, C.POINTER(_ffi.ScalarWallFlux)]
+    L.cfd_set_scalar_buoyancy.argtypes = [_vp, C.c_int32, C.c_float, C.c_float]
+    L.cfd_set_gravity.argtypes = [_vp, C.c_float, C.c_float]
+    L.cfd_buoyancy_get.argtypes = [_vp, C.POINTER(_ffi.Buoyancy)]
+    L.cfd_buoyancy_force_get.argtypes = [_vp, C.POINTER(_ffi.BuoyancyForce)]
     _bound = True
     return L
 
@@ -453,6 +461,36 @@ class GpuSolver:
         st = _ffi.ScalarWallFlux()
         self._call("cfd_scalar_wall_flux_get", int(field), C.byref(st))
         return st
+
+    # -- Boussinesq buoyancy: a scalar field drives the flow ----------------------
+    def set_scalar_buoyancy(self, field, beta, ref=0.0) -> None:
+        """cfd_set_scalar_buoyancy: field ``field`` drives the momentum equation
+        with -density * beta * (phi - ref) * g per unit volume (beta 0, the
+        default: it does not).  Explicit coupling: step() reads the field as it
+        stands; alternate step() and advance_scalars().  enable_scalars()
+        clears it; a checkpoint does not store it."""
+        self._call("cfd_set_scalar_buoyancy", int(field), float(beta), float(ref))
+
+    def set_gravity(self, gx, gy) -> None:
+        """cfd_set_gravity: the gravity vector of the buoyancy term, e.g. (0, -9.81); (0, 0), the default: none."""
+        self._call("cfd_set_gravity", float(gx), float(gy))
+
+    def buoyancy(self) -> dict:
+        """cfd_buoyancy_get: ``g``, ``beta`` and ``ref`` per enabled field, and
+        ``active``: whether the next step() assembles in the buoyant form."""
+        b = _ffi.Buoyancy()
+        self._call("cfd_buoyancy_get", C.byref(b))
+        n = int(b.fields)
+        return dict(g=(float(b.gx), float(b.gy)), beta=[float(v) for v in b.beta[:n]],
+                    ref=[float(v) for v in b.ref[:n]], active=bool(b.active))
+
+    def buoyancy_force(self) -> BuoyancyForce:
+        """cfd_buoyancy_force_get: (fx, fy, fields): the body force the buoyancy
+        term puts on the fluid, summed over the cells in f64 (current fields and
+        density), and the number of driving fields.  (+0, +0) when off."""
+        f = _ffi.BuoyancyForce()
+        self._call("cfd_buoyancy_force_get", C.byref(f))
+        return BuoyancyForce(float(f.force[0]), float(f.force[1]), int(f.fields))
 
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:

@@ -171,8 +171,13 @@ __global__ void __launch_bounds__(kBlock) k_flux_mirror(float* flux_s, const int
   if (m >= 0) flux_s[e] = -flux_s[m];  // owner slots (m < 0) are only read
 }
 
-// coupled_assembly_merged.wgsl:70-463
-__global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) {
+// coupled_assembly_merged.wgsl:70-463.  BUOY: the form with the Boussinesq
+// source (kernels.hpp BuoyancyArgs): one more coalesced 4-byte load per driving
+// field, after the face loop; everything else is the plain form's.  The
+// arguments come by value: by reference the compiler schedules the QUICK
+// branch's loads differently, and k_assemble is to stay the code it was.
+template <bool BUOY>
+__device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
@@ -303,6 +308,18 @@ __global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) {
       sdiag += scoeff;
     }
   }
+  if constexpr (BUOY) {
+    const float vr = vol * c.density;
+#pragma unroll
+    for (int f = 0; f < kMaxBuoyancyFields; ++f) {  // unrolled: every entry a fixed kernel-argument offset
+      if (f < b.n) {
+        const float d = b.f[f].phi[i] - b.f[f].ref;
+        const float fb = vr * (b.f[f].beta * d);
+        rhs_u = rhs_u - fb * b.gx;
+        rhs_v = rhs_v - fb * b.gy;
+      }
+    }
+  }
   const size_t cdslot = (size_t)a.cslot_diag[i] * a.ld + i;
   a.cval_a[cdslot] = make_float2(diag_uv, 0.0f + sdpp);
   a.cval_g[cdslot] = make_float2(sdup, sdvp);
@@ -313,6 +330,10 @@ __global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) {
   a.rhs[3 * (size_t)i + 2] = rhs_p;
   a.dinv_uv[i] = safe_inverse(diag_uv);
   a.dinv_p[i] = safe_inverse(sdiag);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) { assemble_cell<false>(a, BuoyancyArgs{}); }
+__global__ void __launch_bounds__(kBlock) k_assemble_buoyant(AssembleArgs a, BuoyancyArgs b) {
+  assemble_cell<true>(a, b);
 }
 
 // update_fields_from_coupled.wgsl:45-98.  The reference folds max|du|, max|dp|
@@ -397,6 +418,9 @@ void launch_prepare_ordered(const PrepareArgs& a, const int32_t* mirror, uint32_
 }
 void launch_assemble(const AssembleArgs& a, hipStream_t s) {
   if (a.N) hipLaunchKernelGGL(k_assemble, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a);
+}
+void launch_assemble_buoyant(const AssembleArgs& a, const BuoyancyArgs& b, hipStream_t s) {
+  if (a.N) hipLaunchKernelGGL(k_assemble_buoyant, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, b);
 }
 void launch_update_fields(uint32_t N, float au, float ap, const float* x, float2* u, float* p,
                           uint32_t* blockmax, uint32_t* maxbits, uint32_t* host_out, hipStream_t s) {

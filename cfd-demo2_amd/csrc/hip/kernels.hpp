@@ -332,6 +332,26 @@ void launch_prepare(const PrepareArgs& a, hipStream_t s);
 // owner or boundary slot, kept)
 void launch_prepare_ordered(const PrepareArgs& a, const int32_t* mirror, uint32_t slots, hipStream_t s);
 void launch_assemble(const AssembleArgs& a, hipStream_t s);
+// Boussinesq buoyancy (include/cfd2_amd.h "Arithmetic of buoyancy" is the
+// contract), a second kernel argument of the buoyant assembly only: the plain
+// kernel keeps its arguments.  f[0 .. n): the driving fields (beta != 0) in
+// ascending field order; per owned cell, after the face loop and before the
+// stores, one coalesced 4-byte load per entry:
+//   d = phi[i] - ref;  fb = (vol_i * density) * (beta * d)
+//   rhs_u = rhs_u - fb * gx;  rhs_v = rhs_v - fb * gy
+// The matrix, rhs_p and the diagonal inverses keep the plain kernel's bits.
+constexpr int kMaxBuoyancyFields = 4;
+struct BuoyancyField {
+  const float* phi;  // [N] the field as it stands at the launch
+  float beta;
+  float ref;
+};
+struct BuoyancyArgs {
+  BuoyancyField f[kMaxBuoyancyFields];
+  int32_t n;  // entries in use
+  float gx, gy;
+};
+void launch_assemble_buoyant(const AssembleArgs& a, const BuoyancyArgs& b, hipStream_t s);
 // writes per-block max bit patterns to blockmax[2*nb] and the final pair to maxbits[0..1]
 // (and to host_out[0..1], a device view of pinned host memory, when non-null)
 void launch_update_fields(uint32_t N, float alpha_u, float alpha_p, const float* x, float2* u,
@@ -614,6 +634,24 @@ struct ScalarWallFluxArgs {
   double* partial;       // [kWallFluxSums * np]
 };
 void launch_scalar_wall_flux(const ScalarWallFluxArgs& a, hipStream_t s);
+// Read-only body-force diagnostic of the buoyancy the assembly adds (flux.hip
+// BuoyancyArgs), the counterpart of k_flow_diag's wall force: per cell, in f64,
+// from +0 over the driving fields in field order,
+//   m = (((double)vol_i * (double)density) * (double)beta) * ((double)phi_i - (double)ref)
+//   t_x = t_x - m * (double)gx;  t_y = t_y - m * (double)gy
+// Unit partials partial[c * np + unit], c = 0 x, 1 y, in the canonical tree (as
+// launch_scalar_stats writes its sum).
+constexpr int kBuoyancySums = 2;
+struct BuoyancyForceArgs {
+  uint32_t N;
+  const float* vol;
+  BuoyancyArgs b;
+  float density;
+  uint32_t U;       // chunks per unit (RedGeom::U)
+  uint32_t np;      // unit partials per sum
+  double* partial;  // [kBuoyancySums * np]
+};
+void launch_buoyancy_force(const BuoyancyForceArgs& a, hipStream_t s);
 // The assembled system as the solvers read it: the Jacobi row of cell i is
 //   J(phi)_i = (b_i + sum over internal slots k of c_k * phi[other_k]) / diag_i,
 // the sum left to right in slot order (boundary slots skipped), a true

@@ -413,6 +413,40 @@ __global__ void __launch_bounds__(kBlock) k_scalar_wall_flux(ScalarWallFluxArgs 
   if (f < kWallFluxSums) unit_partials(lsum[f], a.U, a.np, N, lb, a.partial + (size_t)f * a.np, threadIdx.x % UB);
 }
 
+// The buoyancy body force (kernels.hpp BuoyancyForceArgs), the shape of
+// k_scalar_stats with two sums: per cell one 4-byte load per driving field and
+// the volume.  Read-only.
+__global__ void __launch_bounds__(kBlock) k_buoyancy_force(BuoyancyForceArgs a) {
+  __shared__ double lsum[kBuoyancySums][4][4];  // [component][chunk q][quarter w]
+  const uint32_t N = a.N;
+  const uint32_t lb = xcd_block();
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double gx = (double)a.b.gx, gy = (double)a.b.gy;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
+    double t[kBuoyancySums] = {0.0, 0.0};
+    if (ci < N) {
+      const double vr = (double)a.vol[ci] * (double)a.density;
+#pragma unroll
+      for (int f = 0; f < kMaxBuoyancyFields; ++f) {  // unrolled: every entry a fixed kernel-argument offset
+        if (f < a.b.n) {
+          const double m = (vr * (double)a.b.f[f].beta) * ((double)a.b.f[f].phi[ci] - (double)a.b.f[f].ref);
+          t[0] = t[0] - m * gx;
+          t[1] = t[1] - m * gy;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBuoyancySums; ++c) {
+      const double r = wave_tree(t[c]);
+      if (lane == 0) lsum[c][q][w] = r;
+    }
+  }
+  __syncthreads();
+  const uint32_t UB = 4 / a.U, c = threadIdx.x / UB;  // thread c UB + u: unit u of component c
+  if (c < kBuoyancySums) unit_partials(lsum[c], a.U, a.np, N, lb, a.partial + (size_t)c * a.np, threadIdx.x % UB);
+}
+
 // ---- BiCGStab on the Jacobi-scaled system (kernels.hpp ScalarKrylovArgs) ----
 // The matrix streams (columns, coefficients, diag, b) are read once per pass
 // and are larger than the Infinity Cache at the sizes this solver is for: they
@@ -710,6 +744,11 @@ void launch_scalar_assemble_limited_bc(const ScalarLimitedArgs& a, const ScalarB
 void launch_scalar_wall_flux(const ScalarWallFluxArgs& a, hipStream_t s) {
   const uint32_t nb = red_blocks(a.N);
   if (nb) hipLaunchKernelGGL(k_scalar_wall_flux, dim3(nb), dim3(kBlock), 0, s, a);
+}
+
+void launch_buoyancy_force(const BuoyancyForceArgs& a, hipStream_t s) {
+  const uint32_t nb = red_blocks(a.N);
+  if (nb) hipLaunchKernelGGL(k_buoyancy_force, dim3(nb), dim3(kBlock), 0, s, a);
 }
 
 void launch_scalar_sweep(const ScalarSweepArgs& a, uint32_t* delta, hipStream_t s) {

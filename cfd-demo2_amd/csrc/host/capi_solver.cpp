@@ -648,6 +648,25 @@ cfd_status cfd_scalar_wall_flux_get(cfd_solver* s, int32_t field, cfd_scalar_wal
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
   return guard([&] { s->s->scalar_wall_flux(field, out); });
 }
+cfd_status cfd_set_scalar_buoyancy(cfd_solver* s, int32_t field, float beta, float ref) {
+  CHECK_S(s);
+  return guard([&] { s->s->set_buoyancy(field, beta, ref); });
+}
+cfd_status cfd_set_gravity(cfd_solver* s, float gx, float gy) {
+  CHECK_S(s);
+  return guard([&] { s->s->set_gravity(gx, gy); });
+}
+cfd_status cfd_buoyancy_get(const cfd_solver* s, cfd_buoyancy* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  s->s->buoyancy_get(out);
+  return CFD_OK;
+}
+cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->buoyancy_force(out); });
+}
 
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {

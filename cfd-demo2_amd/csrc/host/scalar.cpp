@@ -38,7 +38,8 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   hr_grad = nullptr;
   hr_count = nullptr;
   wf_partial = wf_res = nullptr;
-  for (ScalarField& f : sc_field) f = ScalarField{};
+  bf_partial = bf_res = nullptr;
+  for (ScalarField& f : sc_field) f = ScalarField{};  // every beta back to 0: the step is the plain one again
   if (count == 0) return;
   const size_t ld = topo.ld;
   const size_t nbm = std::max<size_t>(scalar_sweep_blocks(N), 2 * (size_t)red_blocks(N));
@@ -359,6 +360,79 @@ void Solver::scalar_wall_flux(int field, cfd_scalar_wall_flux* out) {
   out->flux = h[0];
   out->area = h[1];
   out->phi_area = h[2];
+}
+
+// ---- Boussinesq buoyancy ----
+void Solver::set_buoyancy(int field, float beta, float ref) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no buoyancy on a distributed handle");
+  scalar_check(field);
+  if (!std::isfinite(beta) || !std::isfinite(ref)) throw std::invalid_argument("scalar buoyancy: beta and ref must be finite");
+  sc_field[field].beta = beta;
+  sc_field[field].bref = ref;
+}
+
+void Solver::set_gravity(float gx, float gy) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no gravity on a distributed handle");
+  if (!std::isfinite(gx) || !std::isfinite(gy)) throw std::invalid_argument("gravity: g_x and g_y must be finite");
+  gravity[0] = gx;
+  gravity[1] = gy;
+}
+
+// The field pointers are read here, at launch time: f.phi swaps with sc_alt
+// during an advance.
+bool Solver::buoyancy_args(BuoyancyArgs& b) const {
+  b = BuoyancyArgs{};
+  for (int fi = 0; fi < sc_count; ++fi) {
+    const ScalarField& f = sc_field[fi];
+    if (f.beta != 0.0f) b.f[b.n++] = BuoyancyField{f.phi, f.beta, f.bref};
+  }
+  b.gx = gravity[0];
+  b.gy = gravity[1];
+  return b.n > 0 && (b.gx != 0.0f || b.gy != 0.0f);
+}
+
+void Solver::buoyancy_get(cfd_buoyancy* out) const {
+  std::memset(out, 0, sizeof(*out));
+  out->gx = gravity[0];
+  out->gy = gravity[1];
+  out->fields = sc_count;
+  for (int fi = 0; fi < sc_count; ++fi) {
+    out->beta[fi] = sc_field[fi].beta;
+    out->ref[fi] = sc_field[fi].bref;
+  }
+  BuoyancyArgs b;
+  out->active = buoyancy_args(b) ? 1 : 0;
+}
+
+// Read-only on the current fields, with the current density; launches nothing
+// unless the assembly would take its buoyant form.
+void Solver::buoyancy_force(cfd_buoyancy_force* out) {
+  if (dist()) throw std::invalid_argument("passive scalars run on one GPU only: no buoyancy force on a distributed handle");
+  if (sc_count == 0) throw std::invalid_argument("passive scalars are not enabled (cfd_scalars_enable)");
+  std::memset(out, 0, sizeof(*out));
+  BuoyancyForceArgs a{};
+  const bool on = buoyancy_args(a.b);
+  out->fields = (uint32_t)a.b.n;
+  if (!on) return;
+  CFD_HIP(hipSetDevice(device));
+  if (!bf_partial) {
+    bf_partial = sc_arena.alloc<double>((size_t)kBuoyancySums * pstride);
+    bf_res = sc_arena.alloc<double>(kBuoyancySums);
+  }
+  a.N = N;
+  a.vol = d_vol;
+  a.density = constants.density;
+  a.U = red.U;
+  a.np = pstride;
+  a.partial = bf_partial;
+  launch_buoyancy_force(a, stream);
+  launch_evolution_final(combine(bf_partial, kBuoyancySums), bf_res, stream);
+  check_launch("buoyancy force");
+  double h[kBuoyancySums];
+  CFD_HIP(hipMemcpyAsync(h, bf_res, sizeof(h), hipMemcpyDeviceToHost, stream));
+  sync();
+  out->force[0] = h[0];
+  out->force[1] = h[1];
 }
 
 void Solver::scalar_stats(int field, cfd_scalar_stats* out) {

@@ -375,7 +375,13 @@ void Solver::assemble() {
   a.rhs = rhs;
   a.dinv_uv = dinv_uv;
   a.dinv_p = dinv_p;
-  launch_assemble(a, stream);
+  // Boussinesq buoyancy (scalar.cpp): the buoyant form only when a field drives
+  // and g != 0; otherwise the plain kernel with the arguments it always had
+  BuoyancyArgs b;
+  if (buoyancy_args(b))
+    launch_assemble_buoyant(a, b, stream);
+  else
+    launch_assemble(a, stream);
   check_launch("assemble");
   if (dist()) halo(cell_plan, {{dinv_uv, 1}});  // the Schur prediction reads neighbours' D_u^-1
 }

@@ -608,6 +608,9 @@ struct Solver {
     uint32_t wall_n = 0;                     // wall faces in wall's box
     uint32_t source_n = 0;                   // cells in source's box
     uint32_t* sel = nullptr;                 // [N] the selection image (kernels.hpp ScalarBC), null before the first non-trivial selection
+    // Boussinesq buoyancy (set_buoyancy): the field drives the momentum equation when beta != 0
+    float beta = 0.0f;
+    float bref = 0.0f;
     bool wall_on() const { return wall.kind != 0 && wall_n != 0; }
     bool source_on() const { return source.rate != 0.0f && source_n != 0; }
   };
@@ -635,6 +638,11 @@ struct Solver {
   // that has faces to sum over (null before)
   double* wf_partial = nullptr;    // [kWallFluxSums * pstride] unit partials
   double* wf_res = nullptr;        // [kWallFluxSums] flux, area, phi_area
+  // Buoyancy-force work space, allocated in sc_arena by the first
+  // buoyancy_force with buoyancy on (null before)
+  double* bf_partial = nullptr;    // [kBuoyancySums * pstride] unit partials
+  double* bf_res = nullptr;        // [kBuoyancySums]
+  float gravity[2] = {0.0f, 0.0f}; // set_gravity; kept over scalars_enable (every beta is not)
   std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: the source box)
   float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
   void scalars_enable(int count, const cfd_scalar_config& c);
@@ -653,6 +661,15 @@ struct Solver {
   uint32_t set_scalar_source(int field, const cfd_scalar_source& c);  // returns the cells selected
   void scalar_select(ScalarField& f);   // f.sel from f.wall and f.source (allocates and uploads it when either is on)
   void scalar_wall_flux(int field, cfd_scalar_wall_flux* out);
+  // Boussinesq buoyancy (include/cfd2_amd.h "Arithmetic of buoyancy"): explicit,
+  // one momentum source in the assembly, read from the fields as they stand
+  void set_buoyancy(int field, float beta, float ref);
+  void set_gravity(float gx, float gy);
+  // the driving fields (beta != 0, ascending) with their current pointers and
+  // g; true when the assembly takes its buoyant form (some entry and g != 0)
+  bool buoyancy_args(BuoyancyArgs& b) const;
+  void buoyancy_get(cfd_buoyancy* out) const;
+  void buoyancy_force(cfd_buoyancy_force* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

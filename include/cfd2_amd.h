@@ -544,7 +544,9 @@ cfd_status cfd_dist_plan(const cfd_mesh_view* mesh, int32_t nranks, int32_t rank
  * Wall force: of the fluid on the wall faces selected by cfd_set_force_region,
  * consistent with the assembly (wall face pressure = cell pressure, wall
  * diffusion = viscosity * area / |face centre - cell centre|), n out of the
- * cell: pressure sum p n area, viscous sum viscosity * u * area / dist.       */
+ * cell: pressure sum p n area, viscous sum viscosity * u * area / dist.  With
+ * buoyancy on (the last section) p carries the hydrostatic part, so the
+ * pressure force contains the buoyant lift of the selected walls.           */
 typedef struct cfd_flow_diag {
   double max_speed;        /* sqrt (host, f64) of the device max of (double)u u + (double)v v: the reference's max_vel */
   double max_vorticity;    /* max |omega_i| */
@@ -883,6 +885,70 @@ cfd_status cfd_set_scalar_source(cfd_solver* s, int32_t field, const cfd_scalar_
 /* The wall-flux sums of the field as it stands.  Kind 0 or no selected face:
  * zeros (faces and kind filled in), nothing launched.                        */
 cfd_status cfd_scalar_wall_flux_get(cfd_solver* s, int32_t field, cfd_scalar_wall_flux* out);
+
+/* Boussinesq buoyancy: a scalar field drives the flow.  Each enabled field f
+ * may carry an expansion coefficient beta_f and a reference value ref_f, the
+ * solver one gravity vector g = (g_x, g_y), e.g. (0, -9.81); the momentum
+ * equation gains the force per unit volume
+ *   -density * sum_f beta_f (phi_f - ref_f) * g.
+ * Opt-in: while every beta is 0 or g = (0, 0) (the defaults) cfd_step launches
+ * the assembly kernel it always launched, with the same arguments, and
+ * produces the same bits; otherwise the assembly runs in its buoyant form,
+ * which reads 4 more bytes per cell and driving field.
+ * The coupling is explicit: a cfd_step reads the fields as they stand when it
+ * is called, every Picard iteration of that step the same values, and the
+ * caller alternates cfd_step and cfd_scalar_advance as before.  The splitting
+ * is first order in dt.
+ *
+ * Arithmetic of buoyancy.  All f32, one rounding per operation (nothing
+ * fused), per owned cell i, after the face loop of the assembly and before its
+ * stores, the fields in ascending index order and only those with beta_f != 0:
+ *   d  = phi_f[i] - ref_f
+ *   fb = (vol_i * density) * (beta_f * d)
+ *   rhs_u = rhs_u - fb * g_x
+ *   rhs_v = rhs_v - fb * g_y
+ * Nothing else changes: not the matrix, rhs_p, the diagonal inverses, nor the
+ * Rhie-Chow face flux of prepare_coupled.  The last is a known inconsistency
+ * of collocated schemes: the face flux does not see the body force, so a sharp
+ * front of phi leaves a small spurious divergence next to it
+ * (cfd_flow_diag.max_divergence shows it).
+ * The pressure then carries the hydrostatic part: cfd_flow_diag.force_pressure
+ * contains the buoyant lift of the selected walls.
+ *   body force  cfd_buoyancy_force_get: the counterpart of cfd_flow_diag's wall
+ *              force, the term that closes a momentum budget.  Per cell, in
+ *              f64, from +0 over the driving fields in field order:
+ *                m   = (((double)vol_i * (double)density) * (double)beta_f)
+ *                      * ((double)phi_f[i] - (double)ref_f)
+ *                t_x = t_x - m * (double)g_x;  t_y = t_y - m * (double)g_y
+ *              and the two per-cell terms summed over the cells in the
+ *              canonical order, the tree of cfd_scalar_stats.integral.  phi and
+ *              density are the current ones.  Buoyancy off (no beta != 0, or g =
+ *              (0, 0)): (+0, +0), nothing launched.
+ * cfd_scalars_enable (0, or a re-enable) clears every beta and ref; g stays.
+ * Checkpoints do not store any of it (the file format and its version are
+ * unchanged): a resumed run re-applies cfd_set_scalar_buoyancy, cfd_set_gravity
+ * and cfd_set_scalar.  One GPU only, as the scalars are.                      */
+typedef struct cfd_buoyancy {
+  float gx, gy;
+  int32_t fields;          /* enabled scalar fields */
+  int32_t active;          /* 1: the next cfd_step assembles in the buoyant form */
+  float beta[4];           /* 0 beyond `fields` */
+  float ref[4];
+} cfd_buoyancy;
+typedef struct cfd_buoyancy_force {
+  double force[2];         /* sum over the cells of -vol density sum_f beta_f (phi_f - ref_f) g */
+  uint32_t fields;         /* driving fields (beta != 0) */
+  uint32_t reserved;
+} cfd_buoyancy_force;
+/* Both setters take effect at the next cfd_step.  CFD_ERR_INVALID: a beta,
+ * ref or g that is not finite, a distributed handle, and for the field setter
+ * scalars not enabled or a bad field index.  A refused call changes nothing. */
+cfd_status cfd_set_scalar_buoyancy(cfd_solver* s, int32_t field, float beta, float ref);
+cfd_status cfd_set_gravity(cfd_solver* s, float gx, float gy);
+/* The settings back; never fails on a valid handle.                          */
+cfd_status cfd_buoyancy_get(const cfd_solver* s, cfd_buoyancy* out);
+/* CFD_ERR_INVALID: scalars not enabled, a distributed handle.                */
+cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,16 @@ time, which a kernel trace of this run gives); the extra layout bytes (4 B per
 cell per pass that reads the selection image) over the extra times, left null
 where the extra is below the spread of the two plain runs that bracket it,
 beside the sweep kernel's rate of the same session.  Writes profiles/r12/scalar_bc.json.
+
+--buoyancy: instead, the extra time of a step whose assembly runs in its
+buoyant form (set_scalar_buoyancy + set_gravity: one driving field) over the
+plain step, on one handle in one session under the fixed schedule (5 Picard x
+30 FGMRES, so a step's work does not depend on the state): medians of 10 fenced
+step() calls with buoyancy off, on, and off again; the median of 20 fenced
+buoyancy_force() calls (k_buoyancy_force, the one-block finish and a 16-byte
+read: a whole host call, not the kernel's own time, which a kernel trace of
+this run gives); beside the extra, the expected cost outer iterations x 4 B x N
+at the sweep kernel's rate of the same session.  Writes profiles/r13/buoyancy.json.
 """
 from __future__ import annotations
 
@@ -232,6 +242,74 @@ def wall_row(s, mesh, name, np):
     return out
 
 
+def buoyancy_row(s, mesh, name, np, outer):
+    """Steps with buoyancy off, on and off again on one handle; beta is small, so
+    the flow stays the bench flow while the buoyant kernel does all its work."""
+    x = mesh.arrays()["cell_cx"]
+    dye = np.where(x < 0.5, 1.0, 0.0)
+    n = float(mesh.num_cells())
+    s.enable_scalars(1, max_sweeps=4, check_interval=4)
+    s.set_scalar_params(0, DIFFUSIVITY, 1.0)
+    s.set_scalar(0, dye)
+    s.set_scalar_buoyancy(0, 1e-3, 0.5)
+
+    def steps(on, reps=10):
+        s.set_gravity(0.0, -9.81 if on else 0.0)
+        assert s.buoyancy()["active"] == on
+        ts = []
+        for _ in range(reps + 1):  # the first call is the warm-up
+            s.synchronize()
+            t0 = time.perf_counter()
+            s.step()
+            s.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts[1:]), min(ts[1:]), s.step_layout_bytes()
+
+    off0, off0_min, bytes_off = steps(False)
+    on, on_min, bytes_on = steps(True)
+    off1, off1_min, _ = steps(False)
+    s.set_gravity(0.0, -9.81)
+    ts = []
+    for _ in range(21):
+        s.synchronize()
+        t0 = time.perf_counter()
+        force = s.buoyancy_force()
+        ts.append(time.perf_counter() - t0)
+    f = statistics.median(ts[1:])
+    s.set_gravity(0.0, 0.0)
+
+    def advance(reps, **cfg):
+        s.enable_scalars(1, **cfg)
+        s.set_scalar_params(0, DIFFUSIVITY, 1.0)
+        ts = []
+        for _ in range(reps + 1):
+            s.set_scalar(0, dye)
+            s.synchronize()
+            t0 = time.perf_counter()
+            s.advance_scalars()
+            s.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts[1:])
+
+    t4 = advance(10, max_sweeps=4, check_interval=4)
+    t64 = advance(10, max_sweeps=64, check_interval=64)
+    sweep = (t64 - t4) / 60.0
+    sb = sweep_layout_bytes(mesh)
+    rate = sb / sweep
+    extra, spread = on - 0.5 * (off0 + off1), abs(off1 - off0)
+    extra_bytes = outer * 4.0 * n
+    return dict(config=name, cells=mesh.num_cells(), dt=1e-3, outer_iterations=outer, driving_fields=1,
+                step_off_ms=1e3 * off0, step_off_min_ms=1e3 * off0_min, step_on_ms=1e3 * on, step_on_min_ms=1e3 * on_min,
+                step_off_again_ms=1e3 * off1, step_off_again_min_ms=1e3 * off1_min, extra_us=1e6 * extra,
+                off_spread_us=1e6 * spread, extra_layout_bytes=extra_bytes,
+                step_layout_bytes_off=bytes_off, step_layout_bytes_on=bytes_on,
+                extra_gbs=extra_bytes / extra / 1e9 if extra > spread else None,
+                sweep_us=1e6 * sweep, sweep_layout_bytes=sb, sweep_gbs=rate / 1e9,
+                extra_at_sweep_rate_us=1e6 * extra_bytes / rate,
+                buoyancy_force_call_us=1e6 * f, buoyancy_force_layout_bytes=8.0 * n,
+                buoyancy_force=dict(fx=force.fx, fy=force.fy, fields=force.fields))
+
+
 def fenced(solver, fn, reps=20):
     ts, sweeps = [], []
     for _ in range(reps):
@@ -252,11 +330,12 @@ def main():
     ap.add_argument("--krylov", action="store_true", help="Jacobi against BiCGStab (profiles/r09/scalar_krylov.json)")
     ap.add_argument("--scheme", action="store_true", help="scheme 1 against scheme 0 (profiles/r10/scalar_hr.json)")
     ap.add_argument("--wall", action="store_true", help="the wall-condition forms against the plain ones (profiles/r12/scalar_bc.json)")
+    ap.add_argument("--buoyancy", action="store_true", help="the buoyant step against the plain one (profiles/r13/buoyancy.json)")
     args = ap.parse_args()
-    if args.krylov + args.scheme + args.wall > 1:
-        ap.error("--krylov, --scheme and --wall are separate runs")
+    if args.krylov + args.scheme + args.wall + args.buoyancy > 1:
+        ap.error("--krylov, --scheme, --wall and --buoyancy are separate runs")
     if args.out is None:
-        where = ("r12", "scalar_bc.json") if args.wall else ("r10", "scalar_hr.json") if args.scheme else ("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")
+        where = ("r13", "buoyancy.json") if args.buoyancy else ("r12", "scalar_bc.json") if args.wall else ("r10", "scalar_hr.json") if args.scheme else ("r09", "scalar_krylov.json") if args.krylov else ("r08", "scalar_cost.json")
         args.out = os.path.join(ROOT, "profiles", *where)
     import numpy as np
     from cfd2_amd import GpuSolver, build_id, default_config
@@ -279,6 +358,16 @@ def main():
         s.set_alpha_p(0.3)
         s.set_precond_type(1)
         s.initialize_history()
+        if args.buoyancy:
+            s.step()
+            s.step()
+            row = buoyancy_row(s, mesh, name, np, 5)
+            row["build"] = build_id()
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            s.close()
+            del mesh
+            continue
         if args.scheme or args.wall:
             s.step()
             s.step()
@@ -336,6 +425,19 @@ def main():
         s.close()
         del mesh
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.buoyancy:
+        with open(args.out, "w") as fh:
+            json.dump(dict(what="one handle after 2 steps, fixed schedule 5 Picard x 30 FGMRES / AMG, dt 1e-3, one driving "
+                                "field with beta 1e-3 (tools/scalar_cost.py --buoyancy): medians of 10 fenced step() calls "
+                                "with g = (0, 0) (the plain k_assemble), g = (0, -9.81) (k_assemble_buoyant) and g = (0, 0) "
+                                "again; extra = on - the mean of the two off, extra_gbs null where it is not above their "
+                                "spread; extra layout bytes = outer iterations x 4 B x cells, beside them that many bytes at "
+                                "the sweep kernel's rate of the same session (one sweep = (64 sweeps - 4 sweeps) / 60); "
+                                "buoyancy_force_call_us = the median of 20 fenced buoyancy_force() calls (two launches, a "
+                                "16-byte read, a synchronisation: not the kernel's time)",
+                           rows=rows), fh, indent=1)
+            fh.write("\n")
+        return
     if args.wall:
         with open(args.out, "w") as fh:
             json.dump(dict(what="one field, dt 1e-3, D 1e-4, one handle after 2 steps, every advance from the same step "
