@@ -63,11 +63,10 @@ def _close(s):
 
 
 # ------------------------------------------------------------- assembled system
-def assembled_system(cls, mesh, scheme, time_scheme, density, dt=0.002):
-    """A random u, one cheap step (so that p, d_p and grad_p are non-zero and
-    the Rhie-Chow flux is live), a dt change (BDF2: r = dt/dt_old = 0.75), then
-    debug_prepare_assemble(False) and (True) as
-    test_prepare_assemble_kernels_bitexact runs them."""
+def random_state_solver(cls, mesh, scheme, time_scheme, density, dt=0.002):
+    """A solver with a random u, one cheap step behind it (so that p, d_p and
+    grad_p are non-zero and the Rhie-Chow flux is live) and a dt change (BDF2:
+    r = dt/dt_old = 0.75), the inlet ramp mid-way.  The caller closes it."""
     s = cls(mesh, config=default_config(fixed_outer=1, fixed_inner=6))
     rng = np.random.default_rng(1234)
     s.set_u(rng.uniform(-1, 1, size=(mesh.num_cells(), 2)))
@@ -83,6 +82,13 @@ def assembled_system(cls, mesh, scheme, time_scheme, density, dt=0.002):
     s.step()
     s.set_dt(0.75 * dt)
     s.update_constants()
+    return s
+
+
+def assembled_system(cls, mesh, scheme, time_scheme, density, dt=0.002):
+    """random_state_solver, then debug_prepare_assemble(False) and (True) as
+    test_prepare_assemble_kernels_bitexact runs them."""
+    s = random_state_solver(cls, mesh, scheme, time_scheme, density, dt)
     s.debug_prepare_assemble(False)
     s.debug_prepare_assemble(True)
     sysm = fv.System(mesh, s)
