@@ -304,6 +304,10 @@ class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     ]
 
 
+# cfd_render's field argument (CFD_RENDER_* of include/cfd2_amd.h) by name
+RENDER_FIELDS = {"speed": 0, "ux": 1, "uy": 2, "p": 3, "vorticity": 4, "divergence": 5, "scalar": 6}
+
+
 def default_config(**overrides) -> Config:
     cfg = Config(
         n_outer_correctors=20,

@@ -138,6 +138,11 @@ def _bind():
     L.cfd_set_gravity.argtypes = [_vp, C.c_float, C.c_float]
     L.cfd_buoyancy_get.argtypes = [_vp, C.POINTER(_ffi.Buoyancy)]
     L.cfd_buoyancy_force_get.argtypes = [_vp, C.POINTER(_ffi.BuoyancyForce)]
+    fp = C.POINTER(C.c_float)
+    L.cfd_render_set_polygons.argtypes = [_vp, C.c_uint32, dp, dp, u32p, u32p]
+    L.cfd_render_set_view.argtypes = [_vp, C.c_int32, C.c_int32, dp, u32p]
+    L.cfd_render.argtypes = [_vp, C.c_int32, C.c_int32, fp, u8p, fp]
+    L.cfd_render_owner_get.argtypes = [_vp, u32p]
     _bound = True
     return L
 
@@ -170,6 +175,7 @@ class GpuSolver:
                    "cfd_dist_info")
         self.rank, self.nranks = r.value, n.value
         self.owned = (c0.value, c1.value)  # global cell range this handle owns
+        self._render_polygons, self._render_shape, self.last_render_range = False, None, None  # set_render_mesh, set_view
         self.num_global_cells = ng.value
 
     @classmethod
@@ -491,6 +497,94 @@ class GpuSolver:
         f = _ffi.BuoyancyForce()
         self._call("cfd_buoyancy_force_get", C.byref(f))
         return BuoyancyForce(float(f.force[0]), float(f.force[1]), int(f.fields))
+
+    # -- frames on the device: a cell field as an RGBA8 image ---------------------
+    def set_render_mesh(self, mesh) -> None:
+        """cfd_render_set_polygons: upload ``mesh``'s vertices and CCW cell
+        polygons (Mesh.vertices(), Mesh.topology()); drops the view.  ``None``
+        releases the renderer's device memory.  A MappedMesh has no vertices
+        and cannot render.  One GPU only."""
+        if mesh is None:
+            self._call("cfd_render_set_polygons", 0, None, None, None, None)
+            self._render_polygons, self._render_shape, self.last_render_range = False, None, None
+            return
+        if not hasattr(mesh, "vertices") or not hasattr(mesh, "topology"):
+            raise ValueError("set_render_mesh needs a Mesh with vertices and cell polygons: a "
+                             f"{type(mesh).__name__} has none and cannot render")
+        vx, vy, _ = mesh.vertices()
+        t = mesh.topology()
+        self.set_render_polygons(vx, vy, t["cell_vertex_offsets"], t["cell_vertices"])
+
+    def set_render_polygons(self, vx, vy, cell_vertex_offsets, cell_vertices) -> None:
+        """cfd_render_set_polygons from arrays: one offset per cell plus one,
+        ``cell_vertices[offsets[c]:offsets[c + 1]]`` the CCW polygon of cell c."""
+        vx = np.ascontiguousarray(vx, dtype=np.float64)
+        vy = np.ascontiguousarray(vy, dtype=np.float64)
+        off = np.ascontiguousarray(cell_vertex_offsets, dtype=np.uint32)
+        idx = np.ascontiguousarray(cell_vertices, dtype=np.uint32)
+        if vx.ndim != 1 or vx.shape != vy.shape or len(vx) == 0:
+            raise ValueError("set_render_polygons expects two vertex arrays of one length > 0")
+        if off.shape != (self.num_global_cells + 1,):  # (a distributed handle is refused by the library)
+            raise ValueError("set_render_polygons expects one offset per cell plus one")
+        if idx.ndim != 1 or len(idx) < int(off[-1]):
+            raise ValueError("set_render_polygons: cell_vertices is shorter than cell_vertex_offsets[-1]")
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        self._call("cfd_render_set_polygons", len(vx), vx.ctypes.data_as(dp), vy.ctypes.data_as(dp),
+                   off.ctypes.data_as(up), idx.ctypes.data_as(up))  # a refused call changes nothing
+        self._render_polygons, self._render_shape, self.last_render_range = True, None, None
+
+    def set_view(self, width, height, box=None) -> int:
+        """cfd_render_set_view: build the ownership map of a ``height`` x
+        ``width`` image (1..8192 each) of the world box ``(x0, y0, x1, y1)``;
+        ``None``: the bounding box of the polygons.  Once per view, not per
+        frame.  Returns the pixels that have an owner."""
+        b = None
+        if box is not None:
+            if len(box) != 4:
+                raise ValueError("box = (x0, y0, x1, y1)")
+            b = (C.c_double * 4)(*[float(v) for v in box])
+        n = C.c_uint32(0)
+        self._render_shape = None  # a refused call leaves no view
+        self._call("cfd_render_set_view", int(width), int(height), b, C.byref(n))
+        self._render_shape = (int(height), int(width))
+        return int(n.value)
+
+    def _render_need_view(self):
+        # the output is sized by the view this object set: refused here, in the library's words, without one
+        if not self._render_polygons:
+            raise RuntimeError("render failed: no polygons (set_render_mesh)")
+        if self._render_shape is None:
+            raise RuntimeError("render failed: no view (set_view)")
+        return self._render_shape
+
+    def render(self, field="speed", range=None, scalar=None) -> np.ndarray:
+        """cfd_render: the current state's ``field`` ("speed", "ux", "uy", "p",
+        "vorticity", "divergence", "scalar", or 0..6) as an (H, W, 4) uint8
+        RGBA image, row 0 the top, through the reference's blue-green-red map
+        over ``range`` = (lo, hi); ``None``: the minimum and maximum over all
+        cells, found on the device.  ``scalar``: the field index of "scalar"
+        (default 0).  The range used is kept as ``last_render_range``.  Pixels
+        off the mesh are (0, 0, 0, 0), NaN cells (0, 0, 0, 255)."""
+        if isinstance(field, str):
+            if field not in _ffi.RENDER_FIELDS:
+                raise ValueError(f"render: unknown field {field!r} (one of {', '.join(_ffi.RENDER_FIELDS)})")
+            field = _ffi.RENDER_FIELDS[field]
+        h, w = self._render_need_view()
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        r = None if range is None else (C.c_float * 2)(float(range[0]), float(range[1]))
+        used = (C.c_float * 2)()
+        self._call("cfd_render", int(field), 0 if scalar is None else int(scalar), r,
+                   out.ctypes.data_as(C.POINTER(C.c_uint8)), used)
+        self.last_render_range = (np.float32(used[0]), np.float32(used[1]))
+        return out
+
+    def render_owner(self) -> np.ndarray:
+        """cfd_render_owner_get: the (H, W) uint32 ownership map of the view:
+        the cell under each pixel centre, 0xFFFFFFFF where there is none."""
+        h, w = self._render_need_view()
+        out = np.empty((h, w), dtype=np.uint32)
+        self._call("cfd_render_owner_get", out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
 
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
@@ -825,6 +919,12 @@ class GpuGroup:
     def step_adaptive(self, target_cfl) -> float:
         self.step()
         return self.adapt_dt(target_cfl)
+
+    # frames: one GPU only, as the scalars (set_render_mesh / set_view reach every rank, which refuses)
+    def render(self, *a, **k):
+        raise RuntimeError("render failed: rendering runs on one GPU only: a group's ranks each hold a part of the fields")
+
+    render_owner = render
 
     def step_info(self): return self.ranks[0].step_info()
     def amg_levels(self): return self.ranks[0].amg_levels()

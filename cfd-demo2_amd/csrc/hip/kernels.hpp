@@ -742,4 +742,50 @@ void launch_scalar_krylov_iteration(const ScalarKrylovArgs& a, uint32_t k, uint3
 __host__ __device__ inline uint32_t scalar_value_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
 __host__ __device__ inline uint32_t scalar_key_value(uint32_t key) { return (key & 0x80000000u) ? key & 0x7FFFFFFFu : ~key; }
 
+// ---- render.hip ----
+// A cell field as an RGBA8 image (include/cfd2_amd.h "The picture" is the
+// contract): the ownership map of a view, built once, and per frame one thread
+// per pixel.  All f32, nothing fused.
+constexpr uint32_t kRenderNone = 0xFFFFFFFFu;
+// Pixel boxes of at most this many pixels are tested by the cell's own thread;
+// larger cells go to a list and get a wavefront each.  At 16 a thread's loop is
+// at most 16 pixels x the fan, the same order as a face-slot loop (see DESIGN
+// section 5.4 for what was measured).
+constexpr uint32_t kRenderInPlacePixels = 16;
+struct RenderPolys {
+  uint32_t N;
+  const float* vx;      // [num_vertices]
+  const float* vy;
+  const uint32_t* off;  // [N + 1]
+  const uint32_t* idx;  // [off[N]], every entry < num_vertices
+};
+struct RenderView {
+  uint32_t W, H;
+  float x0, y1;  // the left and the top bound
+  float dx, dy;
+};
+// The map while it is built holds owner + 1 (0: none), so that atomicMax
+// yields the largest index; launch_render_map_finish turns it into owner /
+// kRenderNone in place.  counts[0]: the cells listed, counts[1]: the owned
+// pixels (the caller zeroes both and the map).
+void launch_render_map_cells(const RenderPolys& p, const RenderView& v, uint32_t* map, uint32_t* list, uint32_t* counts,
+                             hipStream_t s);
+void launch_render_map_listed(const RenderPolys& p, const RenderView& v, uint32_t* map, const uint32_t* list,
+                              uint32_t nlist, hipStream_t s);
+void launch_render_map_finish(uint32_t* map, uint32_t npix, uint32_t* covered, hipStream_t s);
+struct RenderValue {
+  int32_t mode;     // 0 |u|, 1 u.x, 2 u.y, 3 f
+  const float2* u;  // [N] modes 0..2
+  const float* f;   // [N] mode 3
+};
+inline uint32_t render_range_blocks(uint32_t N) { return (N + 1023u) / 1024u; }
+// keys[0], keys[1] = the minimum and the maximum of the value over the N cells
+// as scalar_value_key keys, NaN cells ignored (none left: ~0 and 0).
+// blockmm: [2 * render_range_blocks(N)] scratch.
+void launch_render_range(const RenderValue& f, uint32_t N, uint32_t* blockmm, uint32_t* keys, hipStream_t s);
+// One frame: rgba[q] = the packed pixel q (R in the low byte).  keys != null:
+// the range is decoded from them (keys[0] > keys[1]: (0, 1)), else (lo, hi).
+void launch_render_shade(const RenderValue& f, const uint32_t* map, uint32_t npix, const uint32_t* keys, float lo,
+                         float hi, uint32_t* rgba, hipStream_t s);
+
 }  // namespace cfd2

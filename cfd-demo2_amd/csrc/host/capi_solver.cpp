@@ -668,6 +668,31 @@ cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out) {
   return guard([&] { s->s->buoyancy_force(out); });
 }
 
+// ------------------------------------------------------- frames on the device
+cfd_status cfd_render_set_polygons(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
+                                   const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices) {
+  CHECK_S(s);
+  return guard([&] { s->s->render_set_polygons(num_vertices, vx, vy, cell_vertex_offsets, cell_vertices); });
+}
+cfd_status cfd_render_set_view(cfd_solver* s, int32_t width, int32_t height, const double box[4], uint32_t* covered) {
+  CHECK_S(s);
+  return guard([&] {
+    const uint32_t n = s->s->render_set_view(width, height, box);
+    if (covered) *covered = n;
+  });
+}
+cfd_status cfd_render(cfd_solver* s, int32_t field, int32_t scalar_index, const float range[2], uint8_t* rgba,
+                      float used_range[2]) {
+  CHECK_S(s);
+  if (!rgba) return set_error(CFD_ERR_INVALID, "null rgba");
+  return guard([&] { s->s->render(field, scalar_index, range, rgba, used_range); });
+}
+cfd_status cfd_render_owner_get(cfd_solver* s, uint32_t* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->render_owner(out); });
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

@@ -670,6 +670,27 @@ struct Solver {
   bool buoyancy_args(BuoyancyArgs& b) const;
   void buoyancy_get(cfd_buoyancy* out) const;
   void buoyancy_force(cfd_buoyancy_force* out);
+  // ---- frames on the device (render.cpp; kernels.hpp "render.hip") ----
+  // Opt-in and read-only: nothing below is allocated before render_set_polygons,
+  // and step() launches none of it.  One GPU only.  rd_arena holds what depends
+  // on the polygons, rd_view_arena the map and the image of the current view
+  // size; render_set_polygons(0, ...) releases both.
+  DeviceArena rd_arena, rd_view_arena;
+  RenderPolys rd_polys{};          // N = 0: no polygons
+  float rd_bounds[4] = {};         // x0, y0, x1, y1 of the polygons' vertices (f32)
+  uint32_t* rd_list = nullptr;     // [N] the cells that take the wavefront path
+  uint32_t* rd_counts = nullptr;   // [4] listed cells, owned pixels, the auto range's two keys
+  uint32_t* rd_blockmm = nullptr;  // [2 * render_range_blocks(N)]
+  RenderView rd_view{};            // W = 0: no view
+  size_t rd_pixels = 0;            // pixels rd_map / rd_image hold
+  uint32_t* rd_map = nullptr;      // [H * W] owner or kRenderNone
+  uint32_t* rd_image = nullptr;    // [H * W] packed RGBA8
+  uint32_t rd_listed = 0;          // cells of the current view's list
+  void render_release();
+  void render_set_polygons(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx);
+  uint32_t render_set_view(int32_t w, int32_t h, const double* box);  // returns the owned pixels
+  void render(int32_t field, int32_t scalar_index, const float* range, uint8_t* rgba, float* used);
+  void render_owner(uint32_t* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

@@ -950,6 +950,102 @@ cfd_status cfd_buoyancy_get(const cfd_solver* s, cfd_buoyancy* out);
 /* CFD_ERR_INVALID: scalars not enabled, a distributed handle.                */
 cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out);
 
+/* ------------------------------------------------------------------------ */
+/* Frames on the device: a cell field as an H x W RGBA8 image, the headless
+ * form of the reference's renderer (src/ui/cfd_renderer.rs fan-triangulates
+ * every cell, cfd_mesh_shader.wgsl colours each fan by the cell's value).  The
+ * picture is a pure function of the state, the cell polygons, a view box and a
+ * value range.  Opt-in and read-only: a handle that never calls
+ * cfd_render_set_polygons allocates and launches nothing new, cfd_step
+ * launches none of it in any case, and nothing a step reads is written.  One
+ * GPU only: handles of cfd_solver_create_dist* and members of a group of more
+ * than one rank return CFD_ERR_INVALID.  Checkpoints store none of it: the
+ * polygons and the view are not state.  Not built: the reference's mesh-line
+ * overlay (fs_solid), other colour maps, anti-aliasing.
+ *
+ * The picture.  All f32, one rounding per operation (nothing fused).
+ *   polygons   cfd_mesh_view has no vertices; the caller uploads the mesh's
+ *              vertex arrays and the CCW cell polygons (cfd_mesh_get_vertices,
+ *              cfd_mesh_get_topology).  Vertices are rounded to f32 once.  Cell
+ *              c is the union of its fan triangles (v_0, v_i, v_i+1), 1 <= i <=
+ *              n - 2 (build_mesh_vertices); fewer than 3 vertices: nothing.
+ *   view       a world box [x0, x1] x [y0, y1], each bound rounded to f32 once,
+ *              x1 > x0 and y1 > y0 after the rounding; the default is the
+ *              bounding box of the polygons' vertices (compute_bounds), with no
+ *              aspect correction.  1 <= W, H <= 8192.
+ *                dx = (x1 - x0) / W;  dy = (y1 - y0) / H
+ *              (both must come out > 0).  Pixel (row j, column i) has the centre
+ *                px = x0 + (i + 0.5) * dx;  py = y1 - (j + 0.5) * dy
+ *              with i, j and the 0.5 exact in f32: row 0 is the top.
+ *   edges      the edge function of an edge between vertex INDICES a < b is
+ *                E(p) = (xb - xa) * (py - ya) - (yb - ya) * (px - xa);
+ *              an edge traversed from b to a uses -E, so the two cells that
+ *              share an edge see exact negations and the closed tests below
+ *              leave no crack between them.  (a == b: E as written, which is 0.)
+ *   triangles  a triangle (v_0, v_i, v_i+1) has the edge values e_1, e_2, e_3 of
+ *              its edges v_0 -> v_i, v_i -> v_i+1, v_i+1 -> v_0.  It owns p if
+ *              all three are >= 0, or if all three are <= 0 (both windings are
+ *              drawn, as a rasteriser without culling does).  A triangle whose
+ *              e_1 at its own third vertex v_i+1 is 0 has no area and is skipped.
+ *   candidates a cell is tested against the pixels of its pixel box only.  With
+ *              [mnx, mxx] x [mny, mxy] the bounds of its vertices (a NaN
+ *              coordinate is ignored by the comparisons),
+ *                i from floor((mnx - x0) / dx - 0.5) to ceil((mxx - x0) / dx - 0.5)
+ *                j from floor((y1 - mxy) / dy - 0.5) to ceil((y1 - mny) / dy - 0.5)
+ *              clipped to the image: every centre inside the bounds and up to
+ *              one more pixel per side.  It is part of the definition, so that
+ *              the map does not depend on how an implementation culls.
+ *   owner      a pixel belongs to the LARGEST cell index among the cells that
+ *              own its centre, to none (UINT32_MAX) if there are none.  That
+ *              rule makes the map independent of scheduling.
+ *   value      field 0 speed sqrt(u.x * u.x + u.y * u.y) (the shader's mode 1;
+ *              the f32 square root correctly rounded), 1 u.x, 2 u.y, 3 p,
+ *              4 vorticity and 5 divergence (cfd_get_derived's f32 values),
+ *              6 scalar field `scalar_index`.
+ *   colour     cfd_mesh_shader.wgsl:60-93; every pixel of a fan has the same
+ *              cell, so the interpolated value is the cell's value.
+ *                r = hi - lo;  safe = |r| < 1e-10 ? 1 : r;  q = (val - lo) / safe
+ *              (a true division).  q is NaN (a NaN value, or a range that makes
+ *              one): the pixel is (0, 0, 0, 255).  Otherwise t = q < 0 ? 0 :
+ *              (q > 1 ? 1 : q) and
+ *                t < 0.5:    s = t * 2;          (R, G, B) = (0, s, 1 - s)
+ *                otherwise:  s = (t - 0.5) * 2;  (R, G, B) = (s, 1 - s, 0)
+ *              each channel the byte (uint8)(c * 255 + 0.5), alpha 255.  A pixel
+ *              without an owner is (0, 0, 0, 0).  (The reference leaves the
+ *              8-bit rounding to its render target; this one is stated here.)
+ *   auto range with no range given, lo and hi are the minimum and the maximum of
+ *              the field over ALL cells, on or off the image, NaN cells ignored
+ *              (what app.rs does on the host before it draws), found on the
+ *              device over cfd_scalar_stats' order-preserving keys (so -0 <
+ *              +0).  No cell without a NaN: (0, 1).  The range used is returned.
+ * Bytes: rgba[4 * (j * W + i) + k], k = 0 R, 1 G, 2 B, 3 A.                   */
+enum { CFD_RENDER_SPEED = 0, CFD_RENDER_UX = 1, CFD_RENDER_UY = 2, CFD_RENDER_P = 3, CFD_RENDER_VORTICITY = 4,
+       CFD_RENDER_DIVERGENCE = 5, CFD_RENDER_SCALAR = 6 };
+/* Uploads the polygons of the handle's N cells (the first call allocates the
+ * renderer's own device memory) and drops the view.  num_vertices 0 releases
+ * everything (the other arguments are ignored; later render calls return
+ * CFD_ERR_INVALID).  CFD_ERR_INVALID: a distributed handle, a null array,
+ * cell_vertex_offsets[0] != 0, offsets that decrease, cell_vertex_offsets[N]
+ * >= 2^31, a vertex index >= num_vertices.  A refused call changes nothing.   */
+cfd_status cfd_render_set_polygons(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
+                                   const uint32_t* cell_vertex_offsets /* [N + 1] */,
+                                   const uint32_t* cell_vertices /* [cell_vertex_offsets[N]] */);
+/* Builds the ownership map of a view: once per (polygons, view), not per
+ * frame.  box = {x0, y0, x1, y1}; null: the polygons' bounds.  *covered
+ * (optional) = the pixels that have an owner.  CFD_ERR_INVALID: no polygons,
+ * a size outside 1..8192, a box that is not finite or empty after rounding; a
+ * refused call leaves the handle without a view.                              */
+cfd_status cfd_render_set_view(cfd_solver* s, int32_t width, int32_t height, const double box[4], uint32_t* covered);
+/* One frame of the current state into rgba[H * W * 4].  range = {lo, hi};
+ * null: the auto range.  used_range (optional) receives the range used.
+ * CFD_ERR_INVALID: no polygons, no view, a field outside 0..6, field 6 with
+ * scalars not enabled or a bad scalar_index.                                  */
+cfd_status cfd_render(cfd_solver* s, int32_t field, int32_t scalar_index, const float range[2], uint8_t* rgba,
+                      float used_range[2]);
+/* The ownership map, out[j * W + i] = the owner or UINT32_MAX: for picking
+ * ("which cell is under the cursor") and for tests.                           */
+cfd_status cfd_render_owner_get(cfd_solver* s, uint32_t* out /* [H * W] */);
+
 #ifdef __cplusplus
 }
 #endif
