@@ -304,6 +304,24 @@ class StateFileHeader(C.Structure):  # cfd_state_file_header (512 bytes)
     ]
 
 
+class ParticleConfig(C.Structure):  # cfd_particle_config
+    _fields_ = [("hop_cap", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class ParticleStats(C.Structure):  # cfd_particle_stats
+    _fields_ = [("count", C.c_uint64 * 5), ("wall_contacts", C.c_uint64), ("hops_total", C.c_uint64),
+                ("hops_max", C.c_uint64), ("capped", C.c_uint64), ("capacity", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("wall_contacts", "hops_total", "hops_max", "capped", "capacity")}
+        d.update({name: int(self.count[k]) for k, name in enumerate(PARTICLE_STATUS)})
+        return d
+
+
+# the status values of a particle slot (CFD_PARTICLE_* of include/cfd2_amd.h) in order
+PARTICLE_STATUS = ("empty", "alive", "exited_outlet", "exited_inlet", "outside")
+
+
 # cfd_render's field argument (CFD_RENDER_* of include/cfd2_amd.h) by name
 RENDER_FIELDS = {"speed": 0, "ux": 1, "uy": 2, "p": 3, "vorticity": 4, "divergence": 5, "scalar": 6}
 
@@ -357,6 +375,8 @@ EXPORTED = [
     "cfd_scalar_scheme_default", "cfd_set_scalar_scheme", "cfd_scalar_scheme_stats_get",
     "cfd_set_scalar_wall", "cfd_set_scalar_source", "cfd_scalar_wall_flux_get",
     "cfd_set_scalar_buoyancy", "cfd_set_gravity", "cfd_buoyancy_get", "cfd_buoyancy_force_get",
+    "cfd_particles_set_mesh", "cfd_particle_config_default", "cfd_particles_enable", "cfd_particles_seed",
+    "cfd_particles_advance", "cfd_particles_get", "cfd_particles_stats_get", "cfd_render_particles",
 ]
 
 _lib = None

@@ -18,6 +18,8 @@ _bound = False
 
 # GpuSolver.buoyancy_force(): the two force components and the number of driving fields
 BuoyancyForce = collections.namedtuple("BuoyancyForce", "fx fy fields")
+# GpuSolver.particles(): float32 x, y and age, uint32 cell and status (CFD_PARTICLE_*), one entry per slot
+Particles = collections.namedtuple("Particles", "x y cell status age")
 
 
 # cfd_exchange_fn / cfd_allgather_fn (include/cfd2_amd.h)
@@ -143,6 +145,15 @@ def _bind():
     L.cfd_render_set_view.argtypes = [_vp, C.c_int32, C.c_int32, dp, u32p]
     L.cfd_render.argtypes = [_vp, C.c_int32, C.c_int32, fp, u8p, fp]
     L.cfd_render_owner_get.argtypes = [_vp, u32p]
+    L.cfd_particles_set_mesh.argtypes = [_vp, C.c_uint32, dp, dp, u32p, u32p, u32p, u32p]
+    L.cfd_particle_config_default.argtypes = [C.POINTER(_ffi.ParticleConfig)]
+    L.cfd_particle_config_default.restype = None
+    L.cfd_particles_enable.argtypes = [_vp, C.c_uint32, C.POINTER(_ffi.ParticleConfig)]
+    L.cfd_particles_seed.argtypes = [_vp, C.c_uint32, C.c_uint32, dp, dp]
+    L.cfd_particles_advance.argtypes = [_vp, C.c_float]
+    L.cfd_particles_get.argtypes = [_vp, C.c_uint32, C.c_uint32, fp, fp, u32p, u32p, fp]
+    L.cfd_particles_stats_get.argtypes = [_vp, C.POINTER(_ffi.ParticleStats)]
+    L.cfd_render_particles.argtypes = [_vp, C.c_uint32, u8p]
     _bound = True
     return L
 
@@ -177,6 +188,7 @@ class GpuSolver:
         self.owned = (c0.value, c1.value)  # global cell range this handle owns
         self._render_polygons, self._render_shape, self.last_render_range = False, None, None  # set_render_mesh, set_view
         self.num_global_cells = ng.value
+        self._particle_capacity = 0  # enable_particles
 
     @classmethod
     def create_dist(cls, mesh, nranks: int, rank: int, unique_id: bytes, device: int = 0,
@@ -586,6 +598,98 @@ class GpuSolver:
         self._call("cfd_render_owner_get", out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
+    # -- tracer particles on the device -------------------------------------------
+    def set_particle_mesh(self, mesh) -> None:
+        """cfd_particles_set_mesh: upload ``mesh``'s vertices, CCW cell polygons
+        and face vertices (Mesh.vertices(), Mesh.topology()); frees the particle
+        set of an earlier mesh.  ``None`` releases the module's device memory.
+        One GPU only."""
+        if mesh is None:
+            self._call("cfd_particles_set_mesh", 0, None, None, None, None, None, None)
+            self._particle_capacity = 0
+            return
+        if not hasattr(mesh, "vertices") or not hasattr(mesh, "topology"):
+            raise ValueError("set_particle_mesh needs a Mesh with vertices and cell polygons: a "
+                             f"{type(mesh).__name__} has none")
+        vx, vy, _ = mesh.vertices()
+        t = mesh.topology()
+        self.set_particle_polygons(vx, vy, t["cell_vertex_offsets"], t["cell_vertices"], t["face_v1"], t["face_v2"])
+
+    def set_particle_polygons(self, vx, vy, cell_vertex_offsets, cell_vertices, face_v1, face_v2) -> None:
+        """cfd_particles_set_mesh from arrays."""
+        vx = np.ascontiguousarray(vx, dtype=np.float64)
+        vy = np.ascontiguousarray(vy, dtype=np.float64)
+        off = np.ascontiguousarray(cell_vertex_offsets, dtype=np.uint32)
+        idx = np.ascontiguousarray(cell_vertices, dtype=np.uint32)
+        v1 = np.ascontiguousarray(face_v1, dtype=np.uint32)
+        v2 = np.ascontiguousarray(face_v2, dtype=np.uint32)
+        if vx.ndim != 1 or vx.shape != vy.shape or len(vx) == 0:
+            raise ValueError("set_particle_polygons expects two vertex arrays of one length > 0")
+        if off.shape != (self.num_global_cells + 1,):  # (a distributed handle is refused by the library)
+            raise ValueError("set_particle_polygons expects one offset per cell plus one")
+        if idx.ndim != 1 or len(idx) < int(off[-1]):
+            raise ValueError("set_particle_polygons: cell_vertices is shorter than cell_vertex_offsets[-1]")
+        # (a distributed handle, which holds a part of the faces, is refused by the library)
+        if self.nranks == 1 and (v1.shape != (self.num_faces,) or v2.shape != (self.num_faces,)):
+            raise ValueError("set_particle_polygons expects two vertex indices per face")
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        self._call("cfd_particles_set_mesh", len(vx), vx.ctypes.data_as(dp), vy.ctypes.data_as(dp),
+                   off.ctypes.data_as(up), idx.ctypes.data_as(up), v1.ctypes.data_as(up), v2.ctypes.data_as(up))
+        self._particle_capacity = 0  # a refused call changes nothing; an accepted one frees the set
+
+    def enable_particles(self, n, hop_cap=64) -> None:
+        """cfd_particles_enable: ``n`` slots (1..2^24), all EMPTY; 0 frees them.
+        ``hop_cap``: the face crossings a particle may make in one advance."""
+        cfg = _ffi.ParticleConfig(hop_cap=int(hop_cap))
+        self._call("cfd_particles_enable", int(n), C.byref(cfg))
+        self._particle_capacity = int(n)
+
+    def seed_particles(self, xy, first=0) -> None:
+        """cfd_particles_seed: overwrite slots ``[first, first + len(xy))`` with
+        the (n, 2) positions ``xy`` (rounded to float32 once), age 0, and locate
+        them on the device.  Re-seeding a ring of slots at a rake every step
+        draws a streakline."""
+        xy = np.asarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("seed_particles expects an (n, 2) array")
+        x, y = np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+        dp = C.POINTER(C.c_double)
+        self._call("cfd_particles_seed", int(first), len(x), x.ctypes.data_as(dp), y.ctypes.data_as(dp))
+
+    def advance_particles(self, dt=None) -> None:
+        """cfd_particles_advance: carry every ALIVE particle through the current
+        velocity field for ``dt`` (None: the dt of the last step)."""
+        self._call("cfd_particles_advance", 0.0 if dt is None else float(dt))
+
+    def particles(self) -> Particles:
+        """cfd_particles_get of every slot: a ``Particles`` tuple of float32 x, y,
+        age and uint32 cell, status arrays."""
+        n = self._particle_capacity
+        if not n:
+            raise RuntimeError("particles failed: particles are not enabled (enable_particles)")
+        x, y, age = (np.empty(n, np.float32) for _ in range(3))
+        cell, status = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        self._call("cfd_particles_get", 0, n, x.ctypes.data_as(fp), y.ctypes.data_as(fp), cell.ctypes.data_as(up),
+                   status.ctypes.data_as(up), age.ctypes.data_as(fp))
+        return Particles(x, y, cell, status, age)
+
+    def particle_stats(self) -> dict:
+        """cfd_particles_stats_get: the slots per status (by name), wall_contacts,
+        hops_total / hops_max / capped of the last advance, and the capacity."""
+        st = _ffi.ParticleStats()
+        self._call("cfd_particles_stats_get", C.byref(st))
+        return st.as_dict()
+
+    def render_particles(self, colour=(255, 255, 255, 255)) -> np.ndarray:
+        """cfd_render_particles: the last ``render()`` frame with every ALIVE
+        particle in the view stamped as one pixel of ``colour`` (R, G, B, A)."""
+        h, w = self._render_need_view()
+        r, g, b, a = (int(v) & 0xFF for v in colour)
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        self._call("cfd_render_particles", r | g << 8 | b << 16 | a << 24, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -832,7 +936,8 @@ class GpuGroup:
         # setters / state writers apply to every rank
         if name.startswith("set_") or name in ("update_constants", "initialize_history",
                                                "profile_enable", "profile_reset", "synchronize",
-                                               "enable_scalars", "scalar_solver_stats", "scalar_scheme_stats"):  # scalars: refused by every rank, one GPU only
+                                               "enable_scalars", "scalar_solver_stats", "scalar_scheme_stats",
+                                               "enable_particles"):  # scalars, particles: refused by every rank, one GPU only
             def f(*a, **k):
                 for r in self.ranks:
                     getattr(r, name)(*a, **k)

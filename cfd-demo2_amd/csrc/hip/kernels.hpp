@@ -16,6 +16,7 @@
 //    the same rounding as the reference's `scale` pass, which is thereby gone).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -787,5 +788,60 @@ void launch_render_range(const RenderValue& f, uint32_t N, uint32_t* blockmm, ui
 // the range is decoded from them (keys[0] > keys[1]: (0, 1)), else (lo, hi).
 void launch_render_shade(const RenderValue& f, const uint32_t* map, uint32_t npix, const uint32_t* keys, float lo,
                          float hi, uint32_t* rgba, hipStream_t s);
+
+// ---- particles.hip ----
+// Tracer particles (include/cfd2_amd.h "The tracers" is the contract): located
+// in the mesh through a bin grid, advanced face to face through the frozen
+// piecewise-constant velocity, counted, stamped into a frame.  All f32, nothing
+// fused; every kernel is one thread per particle, any count (block tails).
+constexpr uint32_t kParticleSignBit = 0x80000000u;  // ParticleMesh::sa: g = -E
+constexpr uint32_t kParticleCapped = 0x80000000u;   // ParticleSet::hops: the last advance hit the hop cap
+constexpr uint32_t kParticleNoCell = 0xFFFFFFFFu;
+struct ParticleMesh {
+  uint32_t N;  // 0: no mesh
+  int wf;
+  const float* vx;      // [num_vertices]
+  const float* vy;
+  const uint32_t* off;  // [N + 1] the CCW polygons (locate)
+  const uint32_t* idx;  // [off[N]]
+  // the two vertices of every face slot, [k * N + c] like FaceSlots: sa the
+  // smaller index, with kParticleSignBit set where the cell's polygon runs from
+  // the larger index to the smaller one (g = -E); sb the larger index
+  const uint32_t* sa;
+  const uint32_t* sb;
+  // the bin grid: nb x nb bins of (sx, sy) from (bx0, by0); bin (i, j)'s cells
+  // are bin_cells[bin_off[j * nb + i] .. bin_off[j * nb + i + 1]), ascending
+  uint32_t nb;
+  float bx0, by0, sx, sy;
+  const uint32_t* bin_off;
+  const uint32_t* bin_cells;
+};
+// the bin of one coordinate (host and device: the listing and the lookup agree)
+__host__ __device__ inline uint32_t particle_bin(float x, float x0, float s, uint32_t nb) {
+  const float f = floorf((x - x0) / s);
+  if (!(f >= 0.0f)) return 0u;  // also a NaN
+  return f > (float)(nb - 1u) ? nb - 1u : (uint32_t)f;
+}
+struct ParticleSet {  // SoA, 4-byte fields, [capacity]
+  uint32_t n;
+  float* x;
+  float* y;
+  uint32_t* cell;
+  uint32_t* status;
+  float* age;
+  uint32_t* contacts;
+  uint32_t* hops;  // of the last advance | kParticleCapped
+};
+// Slots [first, first + count): position (x, y), age 0, no contacts, located.
+void launch_particles_locate(const ParticleMesh& m, const ParticleSet& p, uint32_t first, uint32_t count, const float* x,
+                             const float* y, hipStream_t s);
+void launch_particles_advance(const ParticleMesh& m, const FaceSlots& fs, const float2* u, const ParticleSet& p, float dt,
+                              uint32_t hop_cap, hipStream_t s);
+// out[0..4] the slots per status, [5] wall contacts, [6] hops of the last
+// advance, [7] their maximum over the particles, [8] particles that hit the
+// cap.  The caller zeroes out.
+constexpr int kParticleStats = 9;
+void launch_particles_stats(const ParticleSet& p, unsigned long long* out, hipStream_t s);
+void launch_particles_stamp(const ParticleSet& p, const RenderView& v, uint32_t colour, uint32_t* rgba, hipStream_t s);
 
 }  // namespace cfd2

@@ -693,6 +693,47 @@ cfd_status cfd_render_owner_get(cfd_solver* s, uint32_t* out) {
   return guard([&] { s->s->render_owner(out); });
 }
 
+// ------------------------------------------------------------ tracer particles
+cfd_status cfd_particles_set_mesh(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
+                                  const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices,
+                                  const uint32_t* face_v1, const uint32_t* face_v2) {
+  CHECK_S(s);
+  return guard(
+      [&] { s->s->particles_set_mesh(num_vertices, vx, vy, cell_vertex_offsets, cell_vertices, face_v1, face_v2); });
+}
+void cfd_particle_config_default(cfd_particle_config* out) {
+  if (!out) return;
+  *out = cfd_particle_config{};
+  out->hop_cap = 64;
+}
+cfd_status cfd_particles_enable(cfd_solver* s, uint32_t capacity, const cfd_particle_config* cfg) {
+  CHECK_S(s);
+  return guard([&] { s->s->particles_enable(capacity, cfg); });
+}
+cfd_status cfd_particles_seed(cfd_solver* s, uint32_t first, uint32_t count, const double* x, const double* y) {
+  CHECK_S(s);
+  return guard([&] { s->s->particles_seed(first, count, x, y); });
+}
+cfd_status cfd_particles_advance(cfd_solver* s, float dt) {
+  CHECK_S(s);
+  return guard([&] { s->s->particles_advance(dt); });
+}
+cfd_status cfd_particles_get(cfd_solver* s, uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell,
+                             uint32_t* status, float* age) {
+  CHECK_S(s);
+  return guard([&] { s->s->particles_get(first, count, x, y, cell, status, age); });
+}
+cfd_status cfd_particles_stats_get(cfd_solver* s, cfd_particle_stats* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->particles_stats(out); });
+}
+cfd_status cfd_render_particles(cfd_solver* s, uint32_t rgba_colour, uint8_t* rgba) {
+  CHECK_S(s);
+  if (!rgba) return set_error(CFD_ERR_INVALID, "null rgba");
+  return guard([&] { s->s->render_particles(rgba_colour, rgba); });
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

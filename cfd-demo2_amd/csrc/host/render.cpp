@@ -24,6 +24,7 @@ void Solver::render_release() {
   rd_list = rd_counts = rd_blockmm = rd_map = rd_image = nullptr;
   rd_pixels = 0;
   rd_listed = 0;
+  rd_rendered = false;
 }
 
 void Solver::render_set_polygons(uint32_t nv, const double* vx, const double* vy, const uint32_t* off,
@@ -74,6 +75,7 @@ uint32_t Solver::render_set_view(int32_t w, int32_t h, const double* box) {
   if (dist()) throw std::invalid_argument(kOneGpu);
   if (rd_polys.N == 0) throw std::invalid_argument("render view: no polygons (cfd_render_set_polygons)");
   rd_view = RenderView{};  // a refused or failed call leaves no view
+  rd_rendered = false;
   if (w < 1 || w > 8192 || h < 1 || h > 8192)
     throw std::invalid_argument("render view: width and height must be 1..8192");
   float b[4];
@@ -157,6 +159,7 @@ void Solver::render(int32_t field, int32_t scalar_index, const float* range, uin
   if (keys) CFD_HIP(hipMemcpyAsync(hk, keys, sizeof(hk), hipMemcpyDeviceToHost, stream));
   CFD_HIP(hipMemcpyAsync(rgba, rd_image, rd_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   sync();
+  rd_rendered = true;
   if (!used) return;
   if (range) {
     used[0] = range[0];

@@ -686,11 +686,40 @@ struct Solver {
   uint32_t* rd_map = nullptr;      // [H * W] owner or kRenderNone
   uint32_t* rd_image = nullptr;    // [H * W] packed RGBA8
   uint32_t rd_listed = 0;          // cells of the current view's list
+  bool rd_rendered = false;        // rd_image holds a frame of the current view (render_particles copies it)
   void render_release();
   void render_set_polygons(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx);
   uint32_t render_set_view(int32_t w, int32_t h, const double* box);  // returns the owned pixels
   void render(int32_t field, int32_t scalar_index, const float* range, uint8_t* rgba, float* used);
   void render_owner(uint32_t* out);
+  // ---- tracer particles (particles.cpp; kernels.hpp "particles.hip") ----
+  // Opt-in and read-only like the renderer: nothing below is allocated before
+  // particles_set_mesh, and step() launches none of it.  One GPU only.
+  // pt_mesh_arena holds the mesh upload, pt_arena the particle set,
+  // pt_frame_arena the stamped copy of a frame, pt_seed_arena the seeds'
+  // staging buffer (grown when a seed call brings more than it holds, so a
+  // rake re-seeded every step allocates once); a new or released mesh frees
+  // the set too (its cells refer to the mesh it was located in).
+  DeviceArena pt_mesh_arena, pt_arena, pt_frame_arena, pt_seed_arena;
+  ParticleMesh pt_mesh{};                 // N = 0: no mesh
+  ParticleSet pt_set{};                   // n = 0: not enabled
+  uint32_t pt_hop_cap = 64;
+  unsigned long long* pt_stats = nullptr; // [kParticleStats]
+  uint32_t* pt_frame = nullptr;           // [pt_frame_pixels] packed RGBA8
+  size_t pt_frame_pixels = 0;
+  float* pt_seed = nullptr;               // [2 * pt_seed_cap]: x, then y
+  uint32_t pt_seed_cap = 0;
+  std::vector<float> pt_seed_host;        // the f32 seeds on their way up
+  void particles_free_set();
+  void particles_need(const char* what, uint32_t first, uint32_t count) const;  // throws: distributed, not enabled, range
+  void particles_set_mesh(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx,
+                          const uint32_t* fv1, const uint32_t* fv2);
+  void particles_enable(uint32_t capacity, const cfd_particle_config* cfg);
+  void particles_seed(uint32_t first, uint32_t count, const double* x, const double* y);
+  void particles_advance(float dt);
+  void particles_get(uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell, uint32_t* status, float* age);
+  void particles_stats(cfd_particle_stats* out);
+  void render_particles(uint32_t colour, uint8_t* rgba);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

@@ -1046,6 +1046,137 @@ cfd_status cfd_render(cfd_solver* s, int32_t field, int32_t scalar_index, const 
  * ("which cell is under the cursor") and for tests.                           */
 cfd_status cfd_render_owner_get(cfd_solver* s, uint32_t* out /* [H * W] */);
 
+/* ------------------------------------------------------------------------ */
+/* Tracer particles: a set of massless points that lives on the device, is
+ * located in the mesh there and is carried face to face by the current
+ * velocity field: pathlines, streaklines (re-seed a ring of slots at a rake
+ * every step), residence times (the age).  Opt-in and read-only: a handle that
+ * never calls cfd_particles_set_mesh allocates and launches nothing new,
+ * cfd_step launches none of it in any case, and nothing a step reads is
+ * written.  One GPU only: handles of cfd_solver_create_dist* and members of a
+ * group of more than one rank return CFD_ERR_INVALID.  Checkpoints store none
+ * of it: neither the mesh upload nor the particles are solver state; a caller
+ * who resumes reads the particles with cfd_particles_get before and seeds them
+ * again after.  Beyond the reference, which has no particles.
+ *
+ * The tracers.  All f32, one rounding per operation (nothing fused).
+ *   geometry   as for the picture: vertices rounded to f32 once, and the edge
+ *              function E of an edge between vertex INDICES a < b,
+ *                E(q) = (xb - xa) * (qy - ya) - (yb - ya) * (qx - xa).
+ *              Face slot k of cell c (the k-th entry of the cell's row of
+ *              cell_faces) has the face's two vertices as a < b and a sign
+ *              fixed at upload: the face's vertices are consecutive in the
+ *              cell's CCW polygon, and
+ *                g_k(q) = E(q) where the polygon runs a -> b, -E(q) where b -> a,
+ *              so g_k >= 0 on the cell's side of the face's line.  The two
+ *              cells of a face see exact negations: a point is never strictly
+ *              outside both.
+ *   bins       [bx0, bx1] x [by0, by1] = the f32 bounds of the polygons'
+ *              vertices; nb = min(1024, ceil(sqrt(N))) bins per direction of
+ *                sx = (bx1 - bx0) / nb;  sy = (by1 - by0) / nb
+ *              (both must come out > 0).  bin(x) = floor((x - bx0) / sx) clamped
+ *              to [0, nb - 1], a NaN to 0; likewise in y.  A cell is listed in
+ *              every bin (i, j) with bin(mnx) <= i <= bin(mxx) and bin(mny) <= j
+ *              <= bin(mxy) of its vertices' f32 bounds.
+ *   locate     a point belongs to the LARGEST cell index among the listed
+ *              cells of its bin whose fan triangles own it under the picture's
+ *              closed test ("triangles" above, zero-area triangles skipped):
+ *              the rule of cfd_render_owner_get for a pixel centre.  bin() is
+ *              monotone and a point inside a fan triangle is inside the cell's
+ *              bounds, so the bins change no answer.  No owner: OUTSIDE.
+ *   advance    per ALIVE particle, independently of all others; u is the
+ *              current state's velocity, frozen for the call.  Start: r = dt,
+ *              c = the particle's cell, v = u[c], no excluded slot, hops = 0.
+ *              Repeat:
+ *                e = p + v * r                     (per component: one product, one sum)
+ *                for each slot k < nface[c] but the excluded one, in order:
+ *                  ge = g_k(e);  gp = g_k(p)
+ *                  ha = v.x * (ya - p.y) - v.y * (xa - p.x);  hb likewise for b
+ *                  candidate if ge < 0 and ((ha >= 0 and hb <= 0) or (ha <= 0
+ *                  and hb >= 0)): the end point is beyond the face's line AND
+ *                  the face's two vertices lie on opposite closed sides of the
+ *                  path's line (real segments, not half-planes: cells with moved
+ *                  hanging nodes are not convex, collinear faces share a line)
+ *                  t_k = gp <= 0 ? 0 : gp / (gp - ge)
+ *                the smallest t_k wins, ties to the lowest slot.
+ *                no candidate, but some slot (not the excluded one) has ge < 0 and
+ *                  the cell's fan triangles do not own e (locate's closed test):
+ *                  a path along a face's line, as a wall slide that ends at the
+ *                  face's vertex, can miss every segment by a rounding.  Then
+ *                  every such slot is a candidate (half-planes), same t_k, same
+ *                  choice.
+ *                no candidate: p = e, age = age + r, done.
+ *                hops == hop_cap: the particle stays where it is, the rest of r
+ *                  is dropped (the age does not take it), it counts as capped,
+ *                  done.  This bounds the work, also at a face where the two
+ *                  cells' velocities point at each other.
+ *                otherwise: s = r * t;  p = p + v * s;  age = age + s;
+ *                  r = r - s;  hops = hops + 1; then by the slot's boundary type
+ *                  internal  c = the slot's neighbour, v = u[c], no excluded slot
+ *                  outlet    status EXITED_OUTLET, done: position and age stay
+ *                  inlet     status EXITED_INLET, likewise
+ *                  wall      contacts + 1;  dn = v.x * nx + v.y * ny;
+ *                            v = (v.x - dn * nx, v.y - dn * ny) (the slot's
+ *                            outward normal) until the particle leaves the cell
+ *                            or the call ends; this slot is the excluded one
+ *                            (a second wall of the same cell replaces it).
+ *              The velocity is piecewise constant, so a path is straight inside
+ *              a cell: exact in time for that field, first order in space.
+ *   stamp      an ALIVE particle covers pixel
+ *                i = floor((p.x - x0) / dx);  j = floor((y1 - p.y) / dy)
+ *              of the current view (x0, y1, dx, dy of "view" above) if 0 <= i <
+ *              W and 0 <= j < H, compared in f32.
+ * Status values; cell is the particle's cell (ALIVE), the cell it left through
+ * a boundary face (EXITED_*), UINT32_MAX otherwise.                           */
+enum { CFD_PARTICLE_EMPTY = 0, CFD_PARTICLE_ALIVE = 1, CFD_PARTICLE_EXITED_OUTLET = 2, CFD_PARTICLE_EXITED_INLET = 3,
+       CFD_PARTICLE_OUTSIDE = 4 };
+typedef struct cfd_particle_config {
+  int32_t hop_cap; /* face crossings per particle and advance: 1..65536; 0: the default 64 */
+  int32_t reserved[3];
+} cfd_particle_config;
+void cfd_particle_config_default(cfd_particle_config* out);
+/* Integer counts reduced on the device: independent of any order.             */
+typedef struct cfd_particle_stats {
+  uint64_t count[5];      /* slots per status; they sum to the capacity            */
+  uint64_t wall_contacts; /* over all slots, since each was seeded                 */
+  uint64_t hops_total;    /* face crossings of the last advance                    */
+  uint64_t hops_max;      /* ... the most of one particle                          */
+  uint64_t capped;        /* particles that hit hop_cap in the last advance        */
+  uint64_t capacity;
+} cfd_particle_stats;
+/* Uploads the vertices, the CCW cell polygons and the two vertices of every
+ * face (cfd_mesh_get_vertices, cfd_mesh_get_topology) into the module's own
+ * device memory, with the per-slot vertex pairs and the bin grid built on the
+ * host.  It frees the particle set of an earlier mesh.  num_vertices 0 releases
+ * everything (the other arguments are ignored).  CFD_ERR_INVALID: what
+ * cfd_render_set_polygons refuses, num_vertices >= 2^31, a polygon that is not
+ * counter-clockwise, a face whose two vertices are equal, out of range or not
+ * consecutive in the polygon of a cell that lists it, bounds that are empty or
+ * not finite.  A refused call changes nothing.                                */
+cfd_status cfd_particles_set_mesh(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
+                                  const uint32_t* cell_vertex_offsets /* [N + 1] */,
+                                  const uint32_t* cell_vertices /* [cell_vertex_offsets[N]] */,
+                                  const uint32_t* face_v1 /* [num_faces] */, const uint32_t* face_v2);
+/* A set of `capacity` slots (1..2^24), all EMPTY; 0 frees it.  cfg null: the
+ * defaults.  CFD_ERR_INVALID: no mesh, a capacity or hop_cap out of range.    */
+cfd_status cfd_particles_enable(cfd_solver* s, uint32_t capacity, const cfd_particle_config* cfg);
+/* Overwrites slots [first, first + count): the positions rounded to f32 once,
+ * age 0, no contacts, located on the device (ALIVE in a cell, or OUTSIDE).    */
+cfd_status cfd_particles_seed(cfd_solver* s, uint32_t first, uint32_t count, const double* x, const double* y);
+/* Advances every ALIVE particle by dt; dt <= 0: the dt of the last cfd_step
+ * (CFD_ERR_INVALID before any step).  Asynchronous like cfd_step.             */
+cfd_status cfd_particles_advance(cfd_solver* s, float dt);
+/* Slots [first, first + count); any output may be null.                       */
+cfd_status cfd_particles_get(cfd_solver* s, uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell,
+                             uint32_t* status, float* age);
+cfd_status cfd_particles_stats_get(cfd_solver* s, cfd_particle_stats* out);
+/* The last cfd_render frame of the current view with every ALIVE particle in
+ * the view stamped as one pixel of rgba_colour (R in the low byte), into
+ * rgba[H * W * 4].  All particles store the same value, so the order of the
+ * stores does not matter.  The renderer's own frame is not modified.
+ * CFD_ERR_INVALID: particles not enabled, no view, no frame of this view yet. */
+cfd_status cfd_render_particles(cfd_solver* s, uint32_t rgba_colour, uint8_t* rgba);
+
 #ifdef __cplusplus
 }
 #endif
