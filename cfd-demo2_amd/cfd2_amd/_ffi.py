@@ -322,6 +322,14 @@ class ParticleStats(C.Structure):  # cfd_particle_stats
 PARTICLE_STATUS = ("empty", "alive", "exited_outlet", "exited_inlet", "outside")
 
 
+class TstatsConfig(C.Structure):  # cfd_tstats_config
+    _fields_ = [("second_moments", C.c_int32), ("scalars", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# cfd_tstats_get's kind argument (CFD_TSTATS_* of include/cfd2_amd.h) by name
+TSTATS_KINDS = {"u": 0, "v": 1, "p": 2, "uu": 3, "uv": 4, "vv": 5, "pp": 6, "phi": 7, "phiphi": 8, "uphi": 9, "vphi": 10}
+
+
 # cfd_render's field argument (CFD_RENDER_* of include/cfd2_amd.h) by name
 RENDER_FIELDS = {"speed": 0, "ux": 1, "uy": 2, "p": 3, "vorticity": 4, "divergence": 5, "scalar": 6}
 
@@ -377,6 +385,10 @@ EXPORTED = [
     "cfd_set_scalar_buoyancy", "cfd_set_gravity", "cfd_buoyancy_get", "cfd_buoyancy_force_get",
     "cfd_particles_set_mesh", "cfd_particle_config_default", "cfd_particles_enable", "cfd_particles_seed",
     "cfd_particles_advance", "cfd_particles_get", "cfd_particles_stats_get", "cfd_render_particles",
+    "cfd_tstats_enable", "cfd_tstats_disable", "cfd_tstats_reset", "cfd_tstats_accumulate", "cfd_tstats_info",
+    "cfd_tstats_get", "cfd_tstats_raw_get", "cfd_tstats_raw_set", "cfd_tstats_raw_set_totals",
+    "cfd_monitor_enable", "cfd_monitor_disable", "cfd_monitor_record", "cfd_monitor_count", "cfd_monitor_info",
+    "cfd_monitor_get",
 ]
 
 _lib = None

@@ -154,6 +154,20 @@ def _bind():
     L.cfd_particles_get.argtypes = [_vp, C.c_uint32, C.c_uint32, fp, fp, u32p, u32p, fp]
     L.cfd_particles_stats_get.argtypes = [_vp, C.POINTER(_ffi.ParticleStats)]
     L.cfd_render_particles.argtypes = [_vp, C.c_uint32, u8p]
+    u64p = C.POINTER(C.c_uint64)
+    L.cfd_tstats_enable.argtypes = [_vp, C.POINTER(_ffi.TstatsConfig)]
+    for n in ("cfd_tstats_disable", "cfd_tstats_reset", "cfd_monitor_disable", "cfd_monitor_record"):
+        getattr(L, n).argtypes = [_vp]
+    L.cfd_tstats_accumulate.argtypes = [_vp, C.c_float]
+    L.cfd_tstats_info.argtypes = [_vp, u64p, dp, u32p]
+    L.cfd_tstats_get.argtypes = [_vp, C.c_int32, C.c_int32, dp]
+    L.cfd_tstats_raw_get.argtypes = [_vp, C.c_uint32, dp]
+    L.cfd_tstats_raw_set.argtypes = [_vp, C.c_uint32, dp]
+    L.cfd_tstats_raw_set_totals.argtypes = [_vp, C.c_uint64, C.c_double]
+    L.cfd_monitor_enable.argtypes = [_vp, C.c_uint32, C.c_uint32, u32p, C.c_int32]
+    L.cfd_monitor_count.argtypes = [_vp, u64p, u64p]
+    L.cfd_monitor_info.argtypes = [_vp, u32p, u32p, u32p, C.POINTER(C.c_int32)]
+    L.cfd_monitor_get.argtypes = [_vp, C.c_uint64, C.c_uint64, fp, fp, fp, C.POINTER(_ffi.FlowDiag)]
     _bound = True
     return L
 
@@ -690,6 +704,130 @@ class GpuSolver:
         self._call("cfd_render_particles", r | g << 8 | b << 16 | a << 24, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         return out
 
+    # -- time-averaged fields and Reynolds stresses, accumulated on the device ------
+    def enable_time_stats(self, second_moments=True, scalars=True) -> None:
+        """cfd_tstats_enable: allocate and zero the f64 planes: the means of u, v,
+        p; with ``second_moments`` the M planes of uu, uv, vv, pp; with
+        ``scalars`` every scalar field enabled now (mean and variance, and with
+        second moments the fluxes u phi, v phi).  A second call starts afresh."""
+        cfg = _ffi.TstatsConfig(1 if second_moments else 0, 1 if scalars else 0)
+        self._call("cfd_tstats_enable", C.byref(cfg))
+
+    def disable_time_stats(self) -> None:
+        self._call("cfd_tstats_disable")
+
+    def reset_time_stats(self) -> None:
+        """cfd_tstats_reset: no samples, zero weight, zero planes."""
+        self._call("cfd_tstats_reset")
+
+    def accumulate_time_stats(self, weight=None) -> None:
+        """cfd_tstats_accumulate: the current state enters the statistics with
+        ``weight`` (None: the dt of the last step).  Asynchronous."""
+        self._call("cfd_tstats_accumulate", 0.0 if weight is None else float(weight))
+
+    def time_stats_info(self) -> dict:
+        """cfd_tstats_info: ``samples``, ``total_weight`` and ``planes``."""
+        n, w, p = C.c_uint64(), C.c_double(), C.c_uint32()
+        self._call("cfd_tstats_info", C.byref(n), C.byref(w), C.byref(p))
+        return dict(samples=int(n.value), total_weight=float(w.value), planes=int(p.value))
+
+    def time_stats(self, kind, field=0) -> np.ndarray:
+        """cfd_tstats_get: one float64 value per cell of ``kind``: a mean "u",
+        "v", "p", "phi", or a covariance "uu", "uv", "vv", "pp", "phiphi",
+        "uphi", "vphi" (or 0..10); ``field``: the scalar field of the phi kinds."""
+        if isinstance(kind, str):
+            if kind not in _ffi.TSTATS_KINDS:
+                raise ValueError(f"time_stats: unknown kind {kind!r} (one of {', '.join(_ffi.TSTATS_KINDS)})")
+            kind = _ffi.TSTATS_KINDS[kind]
+        a = np.zeros(self.num_cells)
+        self._call("cfd_tstats_get", int(kind), int(field), a.ctypes.data_as(C.POINTER(C.c_double)))
+        return a
+
+    def export_time_stats(self) -> dict:
+        """The statistics as they stand: ``planes`` (P, N) float64 (cfd_tstats_raw_get
+        of every plane), ``samples`` and ``total_weight``.  Checkpoints do not
+        hold them: keep this next to the state file."""
+        info = self.time_stats_info()
+        planes = np.zeros((info["planes"], self.num_cells))
+        for q in range(info["planes"]):
+            self._call("cfd_tstats_raw_get", q, planes[q].ctypes.data_as(C.POINTER(C.c_double)))
+        return dict(planes=planes, samples=info["samples"], total_weight=info["total_weight"])
+
+    def import_time_stats(self, d) -> None:
+        """Put back what ``export_time_stats`` returned, into statistics enabled the
+        same way: the run continues bit for bit."""
+        planes = np.ascontiguousarray(d["planes"], dtype=np.float64)
+        info = self.time_stats_info()
+        if planes.shape != (info["planes"], self.num_cells):
+            raise ValueError(f"import_time_stats expects planes of shape {(info['planes'], self.num_cells)}: enable "
+                             "the statistics as they were enabled for the export")
+        for q in range(info["planes"]):
+            self._call("cfd_tstats_raw_set", q, planes[q].ctypes.data_as(C.POINTER(C.c_double)))
+        self._call("cfd_tstats_raw_set_totals", int(d["samples"]), float(d["total_weight"]))
+
+    # -- monitor history: probes and the flow diagnostics recorded on the device ----
+    def enable_monitor(self, capacity, probe_cells=(), diagnostics=True) -> None:
+        """cfd_monitor_enable: a ring of ``capacity`` samples (1..2^20) of the
+        cells ``probe_cells`` (at most 1024) and, with ``diagnostics``, of the
+        flow diagnostics."""
+        cells = np.ascontiguousarray(probe_cells, dtype=np.int64).reshape(-1)
+        if cells.size and (cells.min() < 0 or cells.max() > 0xFFFFFFFF):
+            raise ValueError("enable_monitor: probe cells are cell indices")
+        c32 = cells.astype(np.uint32)
+        self._call("cfd_monitor_enable", int(capacity), len(c32), c32.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   1 if diagnostics else 0)
+
+    def disable_monitor(self) -> None:
+        self._call("cfd_monitor_disable")
+
+    def record_monitor(self) -> None:
+        """cfd_monitor_record: one sample of the current state.  Asynchronous:
+        nothing is copied to the host and nothing waits."""
+        self._call("cfd_monitor_record")
+
+    def monitor_count(self) -> tuple:
+        """cfd_monitor_count: (samples ever recorded, samples held)."""
+        t, h = C.c_uint64(), C.c_uint64()
+        self._call("cfd_monitor_count", C.byref(t), C.byref(h))
+        return int(t.value), int(h.value)
+
+    def monitor(self) -> dict:
+        """cfd_monitor_get of every held sample, oldest first: float32 ``time``
+        and ``dt`` (n,), ``probes`` (n, P, 3 + scalar fields): u.x, u.y, p and the
+        fields; ``total``; and with diagnostics ``diag``, a dict of float64
+        arrays by the names of FlowDiag (``region_faces`` uint32), and
+        ``diag_raw``, the n FlowDiag structures as they came."""
+        total, held = self.monitor_count()
+        _, npr, fields, with_diag = self.monitor_info()
+        t, dt = np.zeros(held, np.float32), np.zeros(held, np.float32)
+        fp = C.POINTER(C.c_float)
+        probes = np.zeros((held, npr, 3 + fields), np.float32)
+        diag = (_ffi.FlowDiag * max(held, 1))()
+        if held:
+            self._call("cfd_monitor_get", 0, held, t.ctypes.data_as(fp), dt.ctypes.data_as(fp),
+                       probes.ctypes.data_as(fp), diag if with_diag else None)
+        out = dict(time=t, dt=dt, probes=probes, total=total)
+        if with_diag:
+            raw = [_ffi.FlowDiag.from_buffer_copy(bytes(diag[k])) for k in range(held)]
+            cols = {}
+            for name, ctype in _ffi.FlowDiag._fields_:
+                if name == "reserved":
+                    continue
+                vals = [getattr(d, name) for d in raw]
+                if name in ("force_pressure", "force_viscous"):
+                    cols[name] = np.array([tuple(v) for v in vals], dtype=np.float64).reshape(held, 2)
+                else:
+                    cols[name] = np.array(vals, dtype=np.uint32 if name == "region_faces" else np.float64)
+            out["diag"], out["diag_raw"] = cols, raw
+        return out
+
+    def monitor_info(self) -> tuple:
+        """cfd_monitor_info: (capacity, probes, scalar fields per probe, with diagnostics)."""
+        v = [C.c_uint32() for _ in range(3)]
+        d = C.c_int32()
+        self._call("cfd_monitor_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(d))
+        return int(v[0].value), int(v[1].value), int(v[2].value), bool(d.value)
+
     # -- public status fields of the reference struct -------------------------
     def step_info(self) -> _ffi.StepInfo:
         i = _ffi.StepInfo()
@@ -937,7 +1075,8 @@ class GpuGroup:
         if name.startswith("set_") or name in ("update_constants", "initialize_history",
                                                "profile_enable", "profile_reset", "synchronize",
                                                "enable_scalars", "scalar_solver_stats", "scalar_scheme_stats",
-                                               "enable_particles"):  # scalars, particles: refused by every rank, one GPU only
+                                               "enable_particles", "enable_time_stats", "enable_monitor"):
+            # scalars, particles, time statistics, monitor: refused by every rank, one GPU only
             def f(*a, **k):
                 for r in self.ranks:
                     getattr(r, name)(*a, **k)

@@ -844,4 +844,44 @@ constexpr int kParticleStats = 9;
 void launch_particles_stats(const ParticleSet& p, unsigned long long* out, hipStream_t s);
 void launch_particles_stamp(const ParticleSet& p, const RenderView& v, uint32_t colour, uint32_t* rgba, hipStream_t s);
 
+// ---- timestats.hip ----
+// Per-cell time statistics (include/cfd2_amd.h "Arithmetic of the time
+// statistics" is the contract): one sample of weight w enters every enabled
+// plane in one pass, all f64, nothing fused.  Planes, each [N] at stride ld
+// (even: a lane's two cells are one 16-byte access): 0 m_u, 1 m_v, 2 m_p; with
+// second moments 3 M_uu, 4 M_uv, 5 M_vv, 6 M_pp; then per field f its mean and
+// M_ff, and with second moments M_uf and M_vf.
+constexpr uint32_t kTimeStatsMaxFields = 4;
+inline uint32_t tstats_planes(bool second_moments, uint32_t nf) {
+  return 3u + (second_moments ? 4u : 0u) + nf * (second_moments ? 4u : 2u);
+}
+struct TimeStatsArgs {
+  uint32_t N;
+  uint32_t nf;            // fields, 0..kTimeStatsMaxFields
+  const float2* u;        // [N] the current state
+  const float* p;
+  double* planes;
+  size_t ld;
+  double w, r;            // the sample's weight and w / (W + w), from the host
+  const float* phi[kTimeStatsMaxFields];
+};
+void launch_tstats(const TimeStatsArgs& a, bool second_moments, hipStream_t s);
+// One monitor sample: time_out[0..1] = time, dt; probe_out[t * (3 + ns) + ..] =
+// u.x, u.y, p and the ns fields at cells[t]; diag_out (or null) = the nine words
+// of the flow diagnostics' device result (diag_res: six f64 sums, three maxima).
+constexpr uint32_t kMonitorDiagWords = 9;
+struct MonitorRecordArgs {
+  uint32_t P, ns;
+  const uint32_t* cells;  // [P], every entry < N
+  const float2* u;
+  const float* p;
+  const float* phi[kTimeStatsMaxFields];
+  float time, dt;
+  float* time_out;        // the slot's [2]
+  float* probe_out;       // the slot's [P * (3 + ns)]
+  const uint64_t* diag_res;
+  uint64_t* diag_out;     // the slot's [kMonitorDiagWords], or null
+};
+void launch_monitor_record(const MonitorRecordArgs& a, hipStream_t s);
+
 }  // namespace cfd2

@@ -734,6 +734,89 @@ cfd_status cfd_render_particles(cfd_solver* s, uint32_t rgba_colour, uint8_t* rg
   return guard([&] { s->s->render_particles(rgba_colour, rgba); });
 }
 
+// ------------------------------------------- time statistics, monitor history
+cfd_status cfd_tstats_enable(cfd_solver* s, const cfd_tstats_config* cfg) {
+  CHECK_S(s);
+  return guard([&] { s->s->tstats_enable(cfg); });
+}
+cfd_status cfd_tstats_disable(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] { s->s->tstats_disable(); });
+}
+cfd_status cfd_tstats_reset(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] { s->s->tstats_reset(); });
+}
+cfd_status cfd_tstats_accumulate(cfd_solver* s, float weight) {
+  CHECK_S(s);
+  return guard([&] { s->s->tstats_accumulate(weight); });
+}
+cfd_status cfd_tstats_info(cfd_solver* s, uint64_t* samples, double* total_weight, uint32_t* planes) {
+  CHECK_S(s);
+  return guard([&] {
+    s->s->tstats_need("cfd_tstats_info");
+    if (samples) *samples = s->s->ts_samples;
+    if (total_weight) *total_weight = s->s->ts_W;
+    if (planes) *planes = s->s->ts_np;
+  });
+}
+cfd_status cfd_tstats_get(cfd_solver* s, int32_t kind, int32_t scalar_index, double* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->tstats_get(kind, scalar_index, out); });
+}
+cfd_status cfd_tstats_raw_get(cfd_solver* s, uint32_t plane, double* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->tstats_raw(plane, out, nullptr); });
+}
+cfd_status cfd_tstats_raw_set(cfd_solver* s, uint32_t plane, const double* in) {
+  CHECK_S(s);
+  if (!in) return set_error(CFD_ERR_INVALID, "null in");
+  return guard([&] { s->s->tstats_raw(plane, nullptr, in); });
+}
+cfd_status cfd_tstats_raw_set_totals(cfd_solver* s, uint64_t samples, double total_weight) {
+  CHECK_S(s);
+  return guard([&] { s->s->tstats_set_totals(samples, total_weight); });
+}
+cfd_status cfd_monitor_enable(cfd_solver* s, uint32_t capacity, uint32_t num_probes, const uint32_t* probe_cells,
+                              int32_t with_diag) {
+  CHECK_S(s);
+  return guard([&] { s->s->monitor_enable(capacity, num_probes, probe_cells, with_diag != 0); });
+}
+cfd_status cfd_monitor_disable(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] { s->s->monitor_disable(); });
+}
+cfd_status cfd_monitor_record(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] { s->s->monitor_record(); });
+}
+cfd_status cfd_monitor_count(cfd_solver* s, uint64_t* total, uint64_t* held) {
+  CHECK_S(s);
+  return guard([&] {
+    s->s->monitor_need("cfd_monitor_count");
+    if (total) *total = s->s->mon_total;
+    if (held) *held = std::min<uint64_t>(s->s->mon_total, s->s->mon_cap);
+  });
+}
+cfd_status cfd_monitor_info(cfd_solver* s, uint32_t* capacity, uint32_t* num_probes, uint32_t* scalar_fields,
+                            int32_t* with_diag) {
+  CHECK_S(s);
+  return guard([&] {
+    s->s->monitor_need("cfd_monitor_info");
+    if (capacity) *capacity = s->s->mon_cap;
+    if (num_probes) *num_probes = s->s->mon_P;
+    if (scalar_fields) *scalar_fields = s->s->mon_ns;
+    if (with_diag) *with_diag = s->s->mon_diag ? 1 : 0;
+  });
+}
+cfd_status cfd_monitor_get(cfd_solver* s, uint64_t first, uint64_t count, float* time, float* dt, float* probes,
+                           cfd_flow_diag* diag) {
+  CHECK_S(s);
+  return guard([&] { s->s->monitor_get(first, count, time, dt, probes, diag); });
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

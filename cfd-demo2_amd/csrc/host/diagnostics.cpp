@@ -25,9 +25,7 @@ bool adaptive_dt_rule(double current_dt, double target_cfl, double min_cell_size
   return true;
 }
 
-void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
-  const Range range("flow diagnostics");
-  CFD_HIP(hipSetDevice(device));
+void Solver::flow_diag_alloc(bool fields) {
   const uint32_t nb = red_blocks(N);
   if (!diag_partial) {
     diag_partial = arena.alloc<double>((size_t)kFlowDiagSums * pstride);
@@ -42,6 +40,10 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
     diag_omega = arena.alloc<float>(N);
     diag_div = arena.alloc<float>(N);
   }
+}
+
+void Solver::flow_diag_device(bool fields, bool reduce) {
+  flow_diag_alloc(fields);
   FlowDiagArgs a{};
   a.N = N;
   a.c = constants;
@@ -58,7 +60,7 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
   a.blockmax = diag_blockmax;
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(diag_res + 6);
   launch_flow_diag(a, mx, stream);
-  if (!out) {  // derived fields only: nothing to reduce across ranks, not collective
+  if (!reduce) {  // derived fields only: nothing to reduce across ranks, not collective
     check_launch("flow diagnostics (fields)");
     return;
   }
@@ -70,15 +72,11 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
                  [&] { comm->allgather(diag_res + 6, diag_res + 9, 3 * sizeof(uint64_t), stream); });
   }
   check_launch("flow diagnostics");
-  std::vector<uint64_t> h(9 + 3 * (size_t)R);
-  CFD_HIP(hipMemcpyAsync(h.data(), diag_res, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  sync();
-  uint64_t m[3] = {0, 0, 0};
-  const uint64_t* src = dist() ? h.data() + 9 : h.data() + 6;
-  for (int q = 0; q < R; ++q)  // rank order (a maximum of bit patterns: any order gives the same)
-    for (int j = 0; j < 3; ++j) m[j] = std::max(m[j], src[3 * q + j]);
+}
+
+void Solver::flow_diag_decode(const uint64_t* sumbits, const uint64_t* m, uint32_t faces, cfd_flow_diag* out) {
   double sums[kFlowDiagSums], smax;
-  std::memcpy(sums, h.data(), sizeof(sums));
+  std::memcpy(sums, sumbits, sizeof(sums));
   std::memcpy(&smax, &m[0], sizeof(double));
   const uint32_t ob = (uint32_t)m[1], db = (uint32_t)m[2];
   float omax, dmax;
@@ -94,7 +92,22 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
   out->force_pressure[1] = sums[3];
   out->force_viscous[0] = sums[4];
   out->force_viscous[1] = sums[5];
-  out->region_faces = region_faces;
+  out->region_faces = faces;
+}
+
+void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
+  const Range range("flow diagnostics");
+  CFD_HIP(hipSetDevice(device));
+  flow_diag_device(fields, out != nullptr);
+  if (!out) return;
+  std::vector<uint64_t> h(9 + 3 * (size_t)R);
+  CFD_HIP(hipMemcpyAsync(h.data(), diag_res, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  sync();
+  uint64_t m[3] = {0, 0, 0};
+  const uint64_t* src = dist() ? h.data() + 9 : h.data() + 6;
+  for (int q = 0; q < R; ++q)  // rank order (a maximum of bit patterns: any order gives the same)
+    for (int j = 0; j < 3; ++j) m[j] = std::max(m[j], src[3 * q + j]);
+  flow_diag_decode(h.data(), m, region_faces, out);
 }
 
 void Solver::get_derived(int kind, double* out) {

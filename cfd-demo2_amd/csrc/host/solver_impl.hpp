@@ -582,6 +582,12 @@ struct Solver {
   bool region_on = false;
   uint32_t region_faces = 0;         // selected wall faces, whole mesh
   void flow_diagnostics(cfd_flow_diag* out, bool fields = false);
+  // its two halves: the launches that leave the sums and maxima in diag_res
+  // (reduce false: the pass alone, for the derived fields), and the decoding of
+  // the words read back (sums: the six f64 patterns, m: the three maximum keys)
+  void flow_diag_alloc(bool fields);
+  void flow_diag_device(bool fields, bool reduce);
+  static void flow_diag_decode(const uint64_t* sums, const uint64_t* m, uint32_t faces, cfd_flow_diag* out);
   void get_derived(int kind, double* out);
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
@@ -720,6 +726,43 @@ struct Solver {
   void particles_get(uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell, uint32_t* status, float* age);
   void particles_stats(cfd_particle_stats* out);
   void render_particles(uint32_t colour, uint8_t* rgba);
+  // ---- time statistics and the monitor history (timestats.cpp; kernels.hpp "timestats.hip") ----
+  // Opt-in and read-only like the particles: nothing below is allocated before
+  // tstats_enable / monitor_enable, and step() launches none of it.  One GPU
+  // only.  ts_arena holds the planes, mon_arena the monitor's ring.
+  DeviceArena ts_arena, mon_arena;
+  double* ts_planes = nullptr;     // [ts_np * ts_ld]; null: not enabled
+  uint32_t ts_np = 0;              // planes (tstats_planes)
+  size_t ts_ld = 0;                // plane stride: N rounded up to 32 doubles
+  bool ts_m2 = false;              // second moments
+  bool ts_scalars = false;         // the configuration asked for the scalar fields
+  uint32_t ts_nf = 0;              // fields the planes hold: sc_count at tstats_enable (0 without ts_scalars)
+  double ts_W = 0.0;               // total weight
+  uint64_t ts_samples = 0;
+  void tstats_need(const char* what) const;  // throws: distributed, not enabled
+  void tstats_enable(const cfd_tstats_config* cfg);
+  void tstats_disable();
+  void tstats_reset();
+  void tstats_accumulate(float weight);
+  int tstats_plane_of(int kind, int scalar_index, bool* covariance) const;  // throws: plane off, bad kind / index
+  void tstats_get(int kind, int scalar_index, double* out);
+  void tstats_raw(uint32_t plane, double* out, const double* in);  // one of the two is null
+  void tstats_set_totals(uint64_t samples, double W);
+  // the monitor: a ring of mon_cap slots, sample k in slot k % mon_cap
+  uint32_t mon_cap = 0;            // 0: not enabled
+  uint32_t mon_P = 0, mon_ns = 0;
+  bool mon_diag = false;
+  uint64_t mon_total = 0;          // samples ever recorded
+  uint32_t* mon_cells = nullptr;   // [P]
+  float* mon_time = nullptr;       // [cap][2] time, dt
+  float* mon_probe = nullptr;      // [cap][P][3 + ns]
+  uint64_t* mon_dres = nullptr;    // [cap][kMonitorDiagWords] (with diagnostics)
+  std::vector<uint32_t> mon_faces; // [cap] region_faces at each record (host: the force region is host state)
+  void monitor_need(const char* what) const;
+  void monitor_enable(uint32_t capacity, uint32_t num_probes, const uint32_t* cells, bool with_diag);
+  void monitor_disable();
+  void monitor_record();
+  void monitor_get(uint64_t first, uint64_t count, float* time, float* dt, float* probes, cfd_flow_diag* diag);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

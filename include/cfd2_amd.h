@@ -1177,6 +1177,113 @@ cfd_status cfd_particles_stats_get(cfd_solver* s, cfd_particle_stats* out);
  * CFD_ERR_INVALID: particles not enabled, no view, no frame of this view yet. */
 cfd_status cfd_render_particles(cfd_solver* s, uint32_t rgba_colour, uint8_t* rgba);
 
+/* ------------------------------------------------------------------------ */
+/* Time-averaged fields: per-cell running means of u, v, p and of every scalar
+ * field, and with second moments the Reynolds stresses <u'u'>, <u'v'>, <v'v'>,
+ * <p'p'>, the variances <phi'phi'> and the turbulent fluxes <u'phi'>, <v'phi'>,
+ * accumulated on the device one sample per cfd_tstats_accumulate: what a
+ * caller could otherwise get only by reading the fields back every step.
+ * Opt-in and read-only: a handle that never calls cfd_tstats_enable allocates
+ * and launches nothing new, cfd_step launches none of it in any case, and
+ * nothing a step reads is written.  One GPU only: handles of
+ * cfd_solver_create_dist* and members of a group of more than one rank return
+ * CFD_ERR_INVALID.  Beyond the reference, which has no averages.
+ * Checkpoints: cfd_state_save / cfd_state_load neither store nor touch the
+ * statistics (the file format and its version are unchanged).
+ * cfd_tstats_raw_get / cfd_tstats_raw_set and cfd_tstats_info /
+ * cfd_tstats_raw_set_totals round-trip the f64 planes and the totals exactly,
+ * so a caller who keeps them next to the state file and restores them after
+ * cfd_state_load continues the averages bit for bit.
+ *
+ * Arithmetic of the time statistics.  Everything f64, one rounding per
+ * operation, nothing fused.  It is the weighted incremental (West / Welford)
+ * update: the first sample is exact, and small fluctuations about a large mean
+ * do not cancel.  W is the total weight so far (0 after enable and reset).
+ *   host, once per call:   w = (double)weight;  Wn = W + w;  r = w / Wn;
+ *                          then W = Wn, samples = samples + 1
+ *   per cell i, x_q = (double) of the f32 value, q in {u, v, p, phi_0 ..}:
+ *     d_q = x_q - m_q                 (the old mean)
+ *     m_q = m_q + r * d_q             (the new mean, stored)
+ *     e_q = x_q - m_q                 (the new mean)
+ *     M_uu += (w * d_u) * e_u;  M_uv += (w * d_u) * e_v;
+ *     M_vv += (w * d_v) * e_v;  M_pp += (w * d_p) * e_p
+ *     per field f:  M_ff += (w * d_f) * e_f;  M_uf += (w * d_u) * e_f;
+ *                   M_vf += (w * d_v) * e_f
+ * u, v, p are the current state (what cfd_get_u / cfd_get_p return), phi_f the
+ * field as cfd_get_scalar returns it.  w and r are computed on the host: the
+ * device divides nothing.  A mean is its plane; a covariance is its M plane
+ * divided by W, on the host in f64 after the read-back.  A NaN in a cell makes
+ * that cell's statistics NaN and touches no other cell; no cell's result
+ * depends on another's or on any schedule.
+ * Planes, in this order (cfd_tstats_raw_get / _set index them): 0 m_u, 1 m_v,
+ * 2 m_p; with second moments 3 M_uu, 4 M_uv, 5 M_vv, 6 M_pp; then for every
+ * field in turn its mean and M_ff, and with second moments M_uf and M_vf.    */
+typedef struct cfd_tstats_config {
+  int32_t second_moments;  /* 0: means only; 1: also the M planes of uu, uv, vv, pp                 */
+  int32_t scalars;         /* 0: none; 1: every scalar field enabled NOW: its mean and M_ff, and
+                              with second_moments M_uf and M_vf                                     */
+  int32_t reserved[2];
+} cfd_tstats_config;
+/* cfd_tstats_get kinds; 7..10 take scalar_index                               */
+enum { CFD_TSTATS_U = 0, CFD_TSTATS_V = 1, CFD_TSTATS_P = 2, CFD_TSTATS_UU = 3, CFD_TSTATS_UV = 4, CFD_TSTATS_VV = 5,
+       CFD_TSTATS_PP = 6, CFD_TSTATS_PHI = 7, CFD_TSTATS_PHIPHI = 8, CFD_TSTATS_UPHI = 9, CFD_TSTATS_VPHI = 10 };
+/* Allocates the planes (8 N bytes each, rounded up to 256) and zeroes them and
+ * the totals; cfg null: {1, 1}.  A second call allocates again: the scalar
+ * count is fixed here.  CFD_ERR_INVALID: a flag that is neither 0 nor 1.      */
+cfd_status cfd_tstats_enable(cfd_solver* s, const cfd_tstats_config* cfg);
+cfd_status cfd_tstats_disable(cfd_solver* s); /* frees */
+/* W = 0, samples = 0, every plane zeroed                                      */
+cfd_status cfd_tstats_reset(cfd_solver* s);
+/* One sample of the current state with this weight; weight <= 0: the dt of the
+ * last cfd_step (CFD_ERR_INVALID before any).  Asynchronous like cfd_step.
+ * CFD_ERR_INVALID, and nothing changes: a NaN or infinite weight; with
+ * cfg.scalars, a count of enabled scalar fields other than the one at
+ * cfd_tstats_enable (enable the statistics again).                            */
+cfd_status cfd_tstats_accumulate(cfd_solver* s, float weight);
+/* Any output may be null.                                                     */
+cfd_status cfd_tstats_info(cfd_solver* s, uint64_t* samples, double* total_weight, uint32_t* planes);
+/* CFD_ERR_INVALID: a kind whose plane is not enabled, a scalar_index outside
+ * the fields the statistics hold, no sample yet (W == 0).                     */
+cfd_status cfd_tstats_get(cfd_solver* s, int32_t kind, int32_t scalar_index, double* out /* [N] */);
+cfd_status cfd_tstats_raw_get(cfd_solver* s, uint32_t plane, double* out /* [N] */);
+cfd_status cfd_tstats_raw_set(cfd_solver* s, uint32_t plane, const double* in /* [N] */);
+/* total_weight must be finite and >= 0                                        */
+cfd_status cfd_tstats_raw_set_totals(cfd_solver* s, uint64_t samples, double total_weight);
+
+/* ------------------------------------------------------------------------ */
+/* Monitor history: probe signals and the flow diagnostics recorded on the
+ * device, one sample per cfd_monitor_record, read back whenever the caller
+ * wants them (the lift history, a wake probe for the shedding frequency).
+ * Opt-in, read-only, one GPU only and outside the checkpoint, as the time
+ * statistics above.  A ring: sample number k (from 0) goes to slot k %
+ * capacity, and cfd_monitor_get addresses the samples still held, oldest
+ * first.  A sample holds constants.time and the dt of the last cfd_step (0
+ * before any) as they stand on the host at the call, per probe cell u.x, u.y, p
+ * and the scalar fields enabled when the monitor was enabled (f32, the values
+ * cfd_get_u / cfd_get_p / cfd_get_scalar widen), and with with_diag the device
+ * result of the flow-diagnostics pass at that state, decoded on read-back by
+ * the code cfd_flow_diagnostics uses: the same bytes it would have returned,
+ * the force region of that moment included.                                   */
+/* Replaces an earlier monitor.  CFD_ERR_INVALID, and nothing changes: capacity
+ * outside 1..2^20, num_probes above 1024, a probe cell >= N.                  */
+cfd_status cfd_monitor_enable(cfd_solver* s, uint32_t capacity, uint32_t num_probes,
+                              const uint32_t* probe_cells /* [num_probes] */, int32_t with_diag);
+cfd_status cfd_monitor_disable(cfd_solver* s); /* frees */
+/* Asynchronous: no copy to the host and no synchronisation.  CFD_ERR_INVALID: a
+ * count of enabled scalar fields other than the one at cfd_monitor_enable.    */
+cfd_status cfd_monitor_record(cfd_solver* s);
+/* total: samples ever recorded; held = min(total, capacity).  Either may be null. */
+cfd_status cfd_monitor_count(cfd_solver* s, uint64_t* total, uint64_t* held);
+/* What cfd_monitor_enable fixed: the capacity, the probes, the scalar fields a
+ * probe holds and whether samples carry the diagnostics.  Any may be null.    */
+cfd_status cfd_monitor_info(cfd_solver* s, uint32_t* capacity, uint32_t* num_probes, uint32_t* scalar_fields,
+                            int32_t* with_diag);
+/* Held samples [first, first + count), oldest first.  Any output may be null;
+ * probes is [count][num_probes][3 + scalar fields]; diag is zeroed when the
+ * monitor was enabled without with_diag.                                      */
+cfd_status cfd_monitor_get(cfd_solver* s, uint64_t first, uint64_t count, float* time, float* dt, float* probes,
+                           cfd_flow_diag* diag /* [count] */);
+
 #ifdef __cplusplus
 }
 #endif
