@@ -241,6 +241,17 @@ class BuoyancyForce(C.Structure):  # cfd_buoyancy_force
     _fields_ = [("force", C.c_double * 2), ("fields", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BoundaryVelocity(C.Structure):  # cfd_boundary_velocity
+    _fields_ = [("inlet_faces", C.c_uint32), ("wall_faces", C.c_uint32), ("inlet_scale", C.c_float),
+                ("wall_scale", C.c_float), ("active", C.c_int32), ("reserved", C.c_int32),
+                ("max_normal_removed", C.c_double)]
+
+
+class WallMotion(C.Structure):  # cfd_wall_motion
+    _fields_ = [("torque_pressure", C.c_double), ("torque_viscous", C.c_double), ("power", C.c_double),
+                ("region_faces", C.c_uint32), ("moving_faces", C.c_uint32)]
+
+
 class AmgLevel(C.Structure):  # cfd_amg_level
     _fields_ = [
         ("n", C.c_uint32), ("nc", C.c_uint32), ("nnz", C.c_uint64), ("r_nnz", C.c_uint64),
@@ -383,6 +394,8 @@ EXPORTED = [
     "cfd_scalar_scheme_default", "cfd_set_scalar_scheme", "cfd_scalar_scheme_stats_get",
     "cfd_set_scalar_wall", "cfd_set_scalar_source", "cfd_scalar_wall_flux_get",
     "cfd_set_scalar_buoyancy", "cfd_set_gravity", "cfd_buoyancy_get", "cfd_buoyancy_force_get",
+    "cfd_set_boundary_velocity", "cfd_set_boundary_velocity_scale", "cfd_boundary_velocity_get",
+    "cfd_wall_motion_get",
     "cfd_particles_set_mesh", "cfd_particle_config_default", "cfd_particles_enable", "cfd_particles_seed",
     "cfd_particles_advance", "cfd_particles_get", "cfd_particles_stats_get", "cfd_render_particles",
     "cfd_tstats_enable", "cfd_tstats_disable", "cfd_tstats_reset", "cfd_tstats_accumulate", "cfd_tstats_info",

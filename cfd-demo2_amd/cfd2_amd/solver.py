@@ -18,6 +18,9 @@ _bound = False
 
 # GpuSolver.buoyancy_force(): the two force components and the number of driving fields
 BuoyancyForce = collections.namedtuple("BuoyancyForce", "fx fy fields")
+# GpuSolver.wall_motion(): torques of the pressure and viscous force on the force
+# region's walls, the power its selected moving walls deliver, and the face counts
+WallMotion = collections.namedtuple("WallMotion", "torque_pressure torque_viscous power region_faces moving_faces")
 # GpuSolver.particles(): float32 x, y and age, uint32 cell and status (CFD_PARTICLE_*), one entry per slot
 Particles = collections.namedtuple("Particles", "x y cell status age")
 
@@ -141,6 +144,10 @@ def _bind():
     L.cfd_buoyancy_get.argtypes = [_vp, C.POINTER(_ffi.Buoyancy)]
     L.cfd_buoyancy_force_get.argtypes = [_vp, C.POINTER(_ffi.BuoyancyForce)]
     fp = C.POINTER(C.c_float)
+    L.cfd_set_boundary_velocity.argtypes = [_vp, C.c_uint32, u32p, fp, fp, u32p]
+    L.cfd_set_boundary_velocity_scale.argtypes = [_vp, C.c_float, C.c_float]
+    L.cfd_boundary_velocity_get.argtypes = [_vp, C.POINTER(_ffi.BoundaryVelocity)]
+    L.cfd_wall_motion_get.argtypes = [_vp, C.c_double, C.c_double, C.POINTER(_ffi.WallMotion)]
     L.cfd_render_set_polygons.argtypes = [_vp, C.c_uint32, dp, dp, u32p, u32p]
     L.cfd_render_set_view.argtypes = [_vp, C.c_int32, C.c_int32, dp, u32p]
     L.cfd_render.argtypes = [_vp, C.c_int32, C.c_int32, fp, u8p, fp]
@@ -170,6 +177,18 @@ def _bind():
     L.cfd_monitor_get.argtypes = [_vp, C.c_uint64, C.c_uint64, fp, fp, fp, C.POINTER(_ffi.FlowDiag)]
     _bound = True
     return L
+
+
+def _boundary_faces(mesh):
+    """(face ids, types, f64 centres x, y) of the inlet (1) and wall (3) boundary
+    faces of ``mesh``, copied: the solver keeps no reference to the mesh."""
+    if mesh is None or not hasattr(mesh, "arrays"):
+        return None
+    a = mesh.arrays()
+    bt = np.asarray(a["face_boundary"]) & 3
+    ids = np.nonzero((np.asarray(a["face_neighbor"]) == 0xFFFFFFFF) & ((bt == 1) | (bt == 3)))[0]
+    return (ids.astype(np.uint32), bt[ids].astype(np.uint32), np.array(a["face_cx"][ids], np.float64),
+            np.array(a["face_cy"][ids], np.float64))
 
 
 class GpuSolver:
@@ -203,6 +222,7 @@ class GpuSolver:
         self._render_polygons, self._render_shape, self.last_render_range = False, None, None  # set_render_mesh, set_view
         self.num_global_cells = ng.value
         self._particle_capacity = 0  # enable_particles
+        self._bnd = _boundary_faces(mesh)  # set_inlet_profile, set_wall_motion
 
     @classmethod
     def create_dist(cls, mesh, nranks: int, rank: int, unique_id: bytes, device: int = 0,
@@ -523,6 +543,94 @@ class GpuSolver:
         f = _ffi.BuoyancyForce()
         self._call("cfd_buoyancy_force_get", C.byref(f))
         return BuoyancyForce(float(f.force[0]), float(f.force[1]), int(f.fields))
+
+    # -- prescribed boundary velocities: inlet profiles and moving walls ------------
+    def set_boundary_velocity(self, faces, v) -> int:
+        """cfd_set_boundary_velocity: global face indices ``faces`` (inlet or
+        wall boundary faces) get the velocities ``v`` [n, 2] in place of
+        inlet_velocity * ramp along +x (inlet) or rest (wall); the ramp and the
+        scales still multiply them.  A wall entry loses its normal component
+        (walls stay impermeable).  A later entry replaces an earlier one of the
+        same face; an empty list clears the whole selection.  Takes effect at the
+        next step(); a checkpoint does not store it.  Returns the faces selected
+        afterwards.  One GPU only."""
+        f = np.ascontiguousarray(np.asarray(faces, np.int64).reshape(-1))
+        if f.size and (f.min() < 0 or f.max() > 0xFFFFFFFF):
+            raise ValueError("face index out of range")
+        f = f.astype(np.uint32)
+        vv = np.asarray(v, np.float64).reshape(-1, 2)
+        if len(vv) != len(f):
+            raise ValueError("faces and v differ in length")
+        vx = np.ascontiguousarray(vv[:, 0], np.float32)
+        vy = np.ascontiguousarray(vv[:, 1], np.float32)
+        n = C.c_uint32()
+        fpt = C.POINTER(C.c_float)
+        self._call("cfd_set_boundary_velocity", len(f), f.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   vx.ctypes.data_as(fpt), vy.ctypes.data_as(fpt), C.byref(n))
+        return int(n.value)
+
+    def clear_boundary_velocity(self) -> None:
+        """The empty selection: the next step() launches the plain kernels again."""
+        self._call("cfd_set_boundary_velocity", 0, None, None, None, None)
+
+    def _boundary(self):
+        if self._bnd is None:
+            raise ValueError("this handle was created without a mesh: use set_boundary_velocity(faces, v)")
+        return self._bnd
+
+    def set_inlet_profile(self, fn) -> int:
+        """``fn(x, y)`` -> (u, v), evaluated on the host in float64 at every
+        inlet face centre (arrays in, arrays or scalars out), e.g. a parabolic
+        profile ``lambda x, y: (6 * y * (H - y) / H**2, 0 * y)``.  Returns the
+        faces selected afterwards."""
+        ids, bt, cx, cy = self._boundary()
+        m = bt == 1
+        u, v = fn(cx[m], cy[m])
+        vel = np.stack([np.broadcast_to(np.asarray(u, np.float64), cx[m].shape),
+                        np.broadcast_to(np.asarray(v, np.float64), cx[m].shape)], 1)
+        return self.set_boundary_velocity(ids[m], vel)
+
+    def set_wall_motion(self, box, velocity=(0.0, 0.0), omega=0.0, centre=None) -> int:
+        """Rigid-body motion of the wall faces whose centre (x, y) lies in the
+        closed ``box`` (x0, y0, x1, y1): (U - omega (y - yc), V + omega (x - xc))
+        with ``velocity`` = (U, V) and ``centre`` = (xc, yc) (default: the centre
+        of the box): a rotating cylinder, a moving belt.  Returns the faces
+        selected afterwards."""
+        ids, bt, cx, cy = self._boundary()
+        x0, y0, x1, y1 = (float(t) for t in box)
+        xc, yc = (0.5 * (x0 + x1), 0.5 * (y0 + y1)) if centre is None else (float(centre[0]), float(centre[1]))
+        m = (bt == 3) & (cx >= x0) & (cx <= x1) & (cy >= y0) & (cy <= y1)
+        if not m.any():
+            return int(sum(self.boundary_velocity()[k] for k in ("inlet_faces", "wall_faces")))
+        vel = np.stack([float(velocity[0]) - float(omega) * (cy[m] - yc),
+                        float(velocity[1]) + float(omega) * (cx[m] - xc)], 1)
+        return self.set_boundary_velocity(ids[m], vel)
+
+    def set_boundary_velocity_scale(self, inlet_scale=1.0, wall_scale=1.0) -> None:
+        """cfd_set_boundary_velocity_scale: two factors applied on the device to
+        the selected inlet and wall velocities (a pulsatile inlet, an oscillating
+        rotation: no new upload).  Takes effect at the next step()."""
+        self._call("cfd_set_boundary_velocity_scale", float(inlet_scale), float(wall_scale))
+
+    def boundary_velocity(self) -> dict:
+        """cfd_boundary_velocity_get: the selected inlet and wall faces, the two
+        scales, ``active`` (the next step() runs the BCV kernels) and the largest
+        normal component removed from a wall entry."""
+        b = _ffi.BoundaryVelocity()
+        self._call("cfd_boundary_velocity_get", C.byref(b))
+        return dict(inlet_faces=int(b.inlet_faces), wall_faces=int(b.wall_faces), inlet_scale=float(b.inlet_scale),
+                    wall_scale=float(b.wall_scale), active=bool(b.active),
+                    max_normal_removed=float(b.max_normal_removed))
+
+    def wall_motion(self, x0=0.0, y0=0.0) -> WallMotion:
+        """cfd_wall_motion_get: over the wall faces of set_force_region(): the
+        torque about (x0, y0) of the pressure and of the viscous force of the
+        fluid on them, and the power the selected moving walls deliver to the
+        fluid (-sum F_on_wall . u_wall), in f64."""
+        w = _ffi.WallMotion()
+        self._call("cfd_wall_motion_get", float(x0), float(y0), C.byref(w))
+        return WallMotion(float(w.torque_pressure), float(w.torque_viscous), float(w.power), int(w.region_faces),
+                          int(w.moving_faces))
 
     # -- frames on the device: a cell field as an RGBA8 image ---------------------
     def set_render_mesh(self, mesh) -> None:

@@ -21,8 +21,11 @@ namespace {
 // round q, wavefront w the chunk's quarter w.  Sums: the quarter's shuffle
 // tree, then unit_partials -- the tree of k_evolution_partial.  Maxima as bit
 // patterns (non-negative values order as unsigned integers; a NaN counts 0).
-template <bool FIELDS, bool FORCE>
-__global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
+// BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs): the
+// face value follows prepare_cell<true>, the viscous force of a selected wall
+// slot takes u - ub.
+template <bool FIELDS, bool FORCE, bool BCV>
+__device__ __forceinline__ void flow_diag_block(const FlowDiagArgs& a, const BcvArgs& v) {
   __shared__ double lsum[kFlowDiagSums][4][4];  // [sum][chunk q][quarter w]
   __shared__ unsigned long long lmax[3][4];
   const uint32_t N = a.N;
@@ -49,6 +52,8 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
         pc = a.p[i];
       }
       const uint32_t nf = fs.nface[i];
+      uint32_t brow = 0;
+      if constexpr (BCV) brow = v.sel[i];
       for (uint32_t k = 0; k < nf; ++k) {
         const size_t e = (size_t)k * N + i;
         const uint32_t meta = fs.meta[e];
@@ -56,6 +61,20 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
         const uint32_t bt = meta & kMetaBtypeMask;
         const float area = fs.area[e];
         const float nx = fs.nx[e], ny = fs.ny[e];  // oriented out of this cell
+        bool bsel = false;  // BCV: a selected slot, its velocity (sbx, sby)
+        float sbx = 0.0f, sby = 0.0f;
+        if constexpr (BCV) {
+          if (other == kNoCell && brow != 0u) {
+            const float4 t = v.tab[(size_t)(brow - 1u) * (uint32_t)fs.wf + k];
+            if (t.z != 0.0f) {
+              const float ramp = wsmoothstep(0.0f, c.ramp_time, c.time);
+              const float g = (bt == 1u ? v.inlet_scale : v.wall_scale) * ramp;
+              bsel = true;
+              sbx = t.x * g;
+              sby = t.y * g;
+            }
+          }
+        }
         // face value of u per face type: a copy of prepare_cell's branch (flux.hip;
         // prepare_coupled.wgsl:281-324).  One shared function changed k_prepare's
         // register allocation, so the two copies stay, held together by
@@ -82,6 +101,12 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
           vfu = uc.x;
           vfv = uc.y;
         }
+        if constexpr (BCV) {
+          if (bsel) {
+            vfu = sbx;
+            vfv = sby;
+          }
+        }
         gux += vfu * nx * area;
         guy += vfu * ny * area;
         gvx += vfv * nx * area;
@@ -91,8 +116,15 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
             const double ad = (double)area, dist = (double)fs.dist_e[e];
             fpx += (double)pc * (double)nx * ad;
             fpy += (double)pc * (double)ny * ad;
-            fvx += (double)c.viscosity * (double)uc.x * ad / dist;
-            fvy += (double)c.viscosity * (double)uc.y * ad / dist;
+            double rux = (double)uc.x, ruy = (double)uc.y;  // relative to the wall
+            if constexpr (BCV) {
+              if (bsel) {
+                rux = (double)uc.x - (double)sbx;
+                ruy = (double)uc.y - (double)sby;
+              }
+            }
+            fvx += (double)c.viscosity * rux * ad / dist;
+            fvy += (double)c.viscosity * ruy * ad / dist;
           }
         }
       }
@@ -149,6 +181,80 @@ __global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
     a.blockmax[3 * (size_t)lb + j] = block_of4_max(lmax[j]);
   }
 }
+template <bool FIELDS, bool FORCE>
+__global__ void __launch_bounds__(kBlock) k_flow_diag(FlowDiagArgs a) {
+  flow_diag_block<FIELDS, FORCE, false>(a, BcvArgs{});
+}
+template <bool FIELDS, bool FORCE>
+__global__ void __launch_bounds__(kBlock) k_flow_diag_bcv(FlowDiagArgs a, BcvArgs v) {
+  flow_diag_block<FIELDS, FORCE, true>(a, v);
+}
+
+// The wall-motion sums (kernels.hpp WallMotionArgs), the shape of
+// k_scalar_wall_flux: a cell with a force-region slot walks the set bits of its
+// mask in ascending order, every other cell loads that word alone.  Read-only.
+__global__ void __launch_bounds__(kBlock) k_wall_motion(WallMotionArgs a) {
+  __shared__ double lsum[kWallMotionSums][4][4];  // [sum][chunk q][quarter w]
+  const uint32_t N = a.N;
+  const cfd_constants c = a.c;
+  const FaceSlots fs = a.fs;
+  const uint32_t lb = xcd_block();
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
+    double t[kWallMotionSums] = {0.0, 0.0, 0.0};
+    if (ci < N) {
+      const uint32_t i = (uint32_t)ci;
+      uint32_t walls = a.wall_mask[i];
+      if (walls) {
+        const float2 uc = a.u[i];
+        const float pc = a.p[i];
+        const uint32_t crow = a.crow[i];  // != 0: the host gives every cell of the region a row
+        const uint32_t brow = a.v.sel ? a.v.sel[i] : 0u;
+        while (walls && crow) {
+          const uint32_t k = (uint32_t)__ffs((int)walls) - 1u;
+          walls &= walls - 1u;
+          const size_t e = (size_t)k * N + i;
+          const double ad = (double)fs.area[e], dist = (double)fs.dist_e[e];
+          const float nx = fs.nx[e], ny = fs.ny[e];
+          bool bsel = false;
+          float sbx = 0.0f, sby = 0.0f;
+          if (brow != 0u) {
+            const float4 tb = a.v.tab[(size_t)(brow - 1u) * (uint32_t)fs.wf + k];
+            if (tb.z != 0.0f) {
+              const float g = a.v.wall_scale * wsmoothstep(0.0f, c.ramp_time, c.time);
+              bsel = true;
+              sbx = tb.x * g;
+              sby = tb.y * g;
+            }
+          }
+          const double fpx = (double)pc * (double)nx * ad;
+          const double fpy = (double)pc * (double)ny * ad;
+          double rux = (double)uc.x, ruy = (double)uc.y;
+          if (bsel) {
+            rux = (double)uc.x - (double)sbx;
+            ruy = (double)uc.y - (double)sby;
+          }
+          const double fvx = (double)c.viscosity * rux * ad / dist;
+          const double fvy = (double)c.viscosity * ruy * ad / dist;
+          const double2 fc = a.ctr[(size_t)(crow - 1u) * (uint32_t)fs.wf + k];
+          const double rx = fc.x - a.x0, ry = fc.y - a.y0;
+          t[0] += rx * fpy - ry * fpx;
+          t[1] += rx * fvy - ry * fvx;
+          if (bsel) t[2] -= (fpx + fvx) * (double)sbx + (fpy + fvy) * (double)sby;
+        }
+      }
+    }
+#pragma unroll
+    for (int f = 0; f < kWallMotionSums; ++f) {
+      const double r = wave_tree(t[f]);
+      if (lane == 0) lsum[f][q][w] = r;
+    }
+  }
+  __syncthreads();
+  const uint32_t UB = 4 / a.U, f = threadIdx.x / UB;  // thread f UB + u: unit u of sum f
+  if (f < kWallMotionSums) unit_partials(lsum[f], a.U, a.np, N, lb, a.partial + (size_t)f * a.np, threadIdx.x % UB);
+}
 
 }  // namespace
 
@@ -167,6 +273,28 @@ void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStre
       hipLaunchKernelGGL((k_flow_diag<false, false>), g, b, 0, s, a);
   }
   hipLaunchKernelGGL(k_block_fold<unsigned long long>, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, 3u, 0u, maxout);
+}
+
+void launch_flow_diag_bcv(const FlowDiagArgs& a, const BcvArgs& v, unsigned long long* maxout, hipStream_t s) {
+  const uint32_t nb = red_blocks(a.N);
+  if (nb) {
+    const bool fields = a.omega_out != nullptr, force = a.wall_mask != nullptr;
+    const dim3 g(nb), b(kBlock);
+    if (fields && force)
+      hipLaunchKernelGGL((k_flow_diag_bcv<true, true>), g, b, 0, s, a, v);
+    else if (fields)
+      hipLaunchKernelGGL((k_flow_diag_bcv<true, false>), g, b, 0, s, a, v);
+    else if (force)
+      hipLaunchKernelGGL((k_flow_diag_bcv<false, true>), g, b, 0, s, a, v);
+    else
+      hipLaunchKernelGGL((k_flow_diag_bcv<false, false>), g, b, 0, s, a, v);
+  }
+  hipLaunchKernelGGL(k_block_fold<unsigned long long>, dim3(1), dim3(kBlock), 0, s, a.blockmax, nb, 3u, 0u, maxout);
+}
+
+void launch_wall_motion(const WallMotionArgs& a, hipStream_t s) {
+  const uint32_t nb = red_blocks(a.N);
+  if (nb) hipLaunchKernelGGL(k_wall_motion, dim3(nb), dim3(kBlock), 0, s, a);
 }
 
 }  // namespace cfd2

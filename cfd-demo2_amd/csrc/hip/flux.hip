@@ -13,9 +13,13 @@ namespace {
 // prepare_coupled.wgsl:63-348 — Rhie-Chow face flux, d_p, Green-Gauss grads.
 // Snapshot semantics: reads st (pre-kernel), writes d_p/grad_p to dp_out/gp_out.
 // prepare_cell: cell i's face fluxes (stored) and its new d_p, grad_p, grad_u,
-// grad_v (returned; k_prepare stores them, k_prepare_ordered after a barrier)
-__device__ __forceinline__ void prepare_cell(const PrepareArgs& a, uint32_t i, float& dp_new, float2& gp_new,
-                                             float2& gu_new, float2& gv_new) {
+// grad_v (returned; k_prepare stores them, k_prepare_ordered after a barrier).
+// BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs): one
+// more coalesced 4-byte load per cell, the table only inside a boundary slot's
+// branch of a cell that has a row; everything else is the plain form's.
+template <bool BCV>
+__device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs& v, uint32_t i, float& dp_new,
+                                             float2& gp_new, float2& gu_new, float2& gv_new) {
   const uint32_t N = a.N;
   const cfd_constants c = a.c;
   const FaceSlots fs = a.fs;
@@ -33,12 +37,28 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, uint32_t i, f
   const float2 gpc = a.st.gp[i];
   float gpx = 0.0f, gpy = 0.0f, gux = 0.0f, guy = 0.0f, gvx = 0.0f, gvy = 0.0f;
   const uint32_t nf = fs.nface[i];
+  uint32_t brow = 0;
+  if constexpr (BCV) brow = v.sel[i];
   for (uint32_t k = 0; k < nf; ++k) {
     const size_t e = (size_t)k * N + i;
     const uint32_t meta = fs.meta[e];
     const int32_t other = fs.other[e];
     const uint32_t bt = meta & kMetaBtypeMask;
     const bool own = (meta & kMetaOwner) != 0;
+    bool bsel = false;  // BCV: a selected slot, its velocity (sbx, sby)
+    float sbx = 0.0f, sby = 0.0f;
+    if constexpr (BCV) {
+      if (other == kNoCell && brow != 0u) {
+        const float4 t = v.tab[(size_t)(brow - 1u) * (uint32_t)fs.wf + k];
+        if (t.z != 0.0f) {
+          const float ramp = wsmoothstep(0.0f, c.ramp_time, c.time);
+          const float g = (bt == 1u ? v.inlet_scale : v.wall_scale) * ramp;
+          bsel = true;
+          sbx = t.x * g;
+          sby = t.y * g;
+        }
+      }
+    }
     const float area = fs.area[e];
     const float nx = fs.nx[e], ny = fs.ny[e];  // oriented out of this cell
     // stored face normal, then prepare's geometric re-orientation (wgsl:122-130)
@@ -73,7 +93,13 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, uint32_t i, f
       flux = c.density * (u_n * area + rc_term);
     } else if (bt == 1u) {
       const float ramp = wsmoothstep(0.0f, c.ramp_time, c.time);
-      const float ubx = c.inlet_velocity * ramp, uby = 0.0f;
+      float ubx = c.inlet_velocity * ramp, uby = 0.0f;
+      if constexpr (BCV) {
+        if (bsel) {
+          ubx = sbx;
+          uby = sby;
+        }
+      }
       flux = c.density * (ubx * nfx + uby * nfy) * area;
     } else if (bt == 2u) {
       const float u_n = uc.x * nfx + uc.y * nfy;  // boundary faces are owned by this cell
@@ -116,6 +142,12 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, uint32_t i, f
         vfu = uc.x;
         vfv = uc.y;
       }
+      if constexpr (BCV) {
+        if (bsel) {
+          vfu = sbx;
+          vfv = sby;
+        }
+      }
     }
     gpx += vfp * nx * area;
     gpy += vfp * ny * area;
@@ -134,7 +166,18 @@ __global__ void __launch_bounds__(kBlock) k_prepare(PrepareArgs a) {
   if (i >= a.N) return;
   float dp;
   float2 gp, gu, gv;
-  prepare_cell(a, i, dp, gp, gu, gv);
+  prepare_cell<false>(a, BcvArgs{}, i, dp, gp, gu, gv);
+  a.dp_out[i] = dp;
+  a.gp_out[i] = gp;
+  a.grad_u[i] = gu;
+  a.grad_v[i] = gv;
+}
+__global__ void __launch_bounds__(kBlock) k_prepare_bcv(PrepareArgs a, BcvArgs v) {
+  const uint32_t i = row_id();
+  if (i >= a.N) return;
+  float dp;
+  float2 gp, gu, gv;
+  prepare_cell<true>(a, v, i, dp, gp, gu, gv);
   a.dp_out[i] = dp;
   a.gp_out[i] = gp;
   a.grad_u[i] = gu;
@@ -150,7 +193,7 @@ __global__ void __launch_bounds__(64) k_prepare_ordered(PrepareArgs a) {
     const uint32_t i = b0 + threadIdx.x;
     float dp = 0.0f;
     float2 gp = make_float2(0.0f, 0.0f), gu = gp, gv = gp;
-    if (i < a.N) prepare_cell(a, i, dp, gp, gu, gv);
+    if (i < a.N) prepare_cell<false>(a, BcvArgs{}, i, dp, gp, gu, gv);
     __syncthreads();  // the workgroup's reads complete
     if (i < a.N) {
       a.dp_out[i] = dp;
@@ -176,8 +219,10 @@ __global__ void __launch_bounds__(kBlock) k_flux_mirror(float* flux_s, const int
 // field, after the face loop; everything else is the plain form's.  The
 // arguments come by value: by reference the compiler schedules the QUICK
 // branch's loads differently, and k_assemble is to stay the code it was.
-template <bool BUOY>
-__device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b) {
+// BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs), as in
+// prepare_cell: nothing is added to an interior slot.
+template <bool BUOY, bool BCV>
+__device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b, const BcvArgs v) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
@@ -206,6 +251,8 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
   const float dpc = a.st.dp[i];
   const float2 uc = a.st.u[i];
   const uint32_t nf = fs.nface[i];
+  uint32_t brow = 0;
+  if constexpr (BCV) brow = v.sel[i];
   for (uint32_t k = 0; k < nf; ++k) {
     const size_t e = (size_t)k * N + i;
     const uint32_t meta = fs.meta[e];
@@ -280,7 +327,17 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
       a.sval[(size_t)rank * a.ld + i] = -scoeff;
     } else if (bt == 1u) {
       const float ramp = wsmoothstep(0.0f, c.ramp_time, c.time);
-      const float ubx = c.inlet_velocity * ramp, uby = 0.0f;
+      float ubx = c.inlet_velocity * ramp, uby = 0.0f;
+      if constexpr (BCV) {
+        if (brow != 0u) {
+          const float4 t = v.tab[(size_t)(brow - 1u) * (uint32_t)fs.wf + k];
+          if (t.z != 0.0f) {
+            const float g = v.inlet_scale * ramp;
+            ubx = t.x * g;
+            uby = t.y * g;
+          }
+        }
+      }
       diag_uv += diff_coeff;
       rhs_u += diff_coeff * ubx;
       rhs_v += diff_coeff * uby;
@@ -298,6 +355,16 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
       diag_uv += diff_coeff;
       sdup += area * nx;
       sdvp += area * ny;
+      if constexpr (BCV) {
+        if (brow != 0u) {
+          const float4 t = v.tab[(size_t)(brow - 1u) * (uint32_t)fs.wf + k];
+          if (t.z != 0.0f) {
+            const float g = v.wall_scale * wsmoothstep(0.0f, c.ramp_time, c.time);
+            rhs_u += diff_coeff * (t.x * g);
+            rhs_v += diff_coeff * (t.y * g);
+          }
+        }
+      }
     } else if (bt == 2u) {
       if (flux > 0.0f) diag_uv += flux;
       sdpu += nx * area;
@@ -331,9 +398,17 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
   a.dinv_uv[i] = safe_inverse(diag_uv);
   a.dinv_p[i] = safe_inverse(sdiag);
 }
-__global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) { assemble_cell<false>(a, BuoyancyArgs{}); }
+__global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) {
+  assemble_cell<false, false>(a, BuoyancyArgs{}, BcvArgs{});
+}
 __global__ void __launch_bounds__(kBlock) k_assemble_buoyant(AssembleArgs a, BuoyancyArgs b) {
-  assemble_cell<true>(a, b);
+  assemble_cell<true, false>(a, b, BcvArgs{});
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_bcv(AssembleArgs a, BcvArgs v) {
+  assemble_cell<false, true>(a, BuoyancyArgs{}, v);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_buoyant_bcv(AssembleArgs a, BuoyancyArgs b, BcvArgs v) {
+  assemble_cell<true, true>(a, b, v);
 }
 
 // update_fields_from_coupled.wgsl:45-98.  The reference folds max|du|, max|dp|
@@ -421,6 +496,16 @@ void launch_assemble(const AssembleArgs& a, hipStream_t s) {
 }
 void launch_assemble_buoyant(const AssembleArgs& a, const BuoyancyArgs& b, hipStream_t s) {
   if (a.N) hipLaunchKernelGGL(k_assemble_buoyant, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, b);
+}
+void launch_prepare_bcv(const PrepareArgs& a, const BcvArgs& v, hipStream_t s) {
+  if (a.N) hipLaunchKernelGGL(k_prepare_bcv, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, v);
+}
+void launch_assemble_bcv(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs& v, hipStream_t s) {
+  if (!a.N) return;
+  if (buoy)
+    hipLaunchKernelGGL(k_assemble_buoyant_bcv, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, *buoy, v);
+  else
+    hipLaunchKernelGGL(k_assemble_bcv, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, v);
 }
 void launch_update_fields(uint32_t N, float au, float ap, const float* x, float2* u, float* p,
                           uint32_t* blockmax, uint32_t* maxbits, uint32_t* host_out, hipStream_t s) {

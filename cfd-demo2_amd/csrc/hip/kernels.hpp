@@ -353,6 +353,26 @@ struct BuoyancyArgs {
   float gx, gy;
 };
 void launch_assemble_buoyant(const AssembleArgs& a, const BuoyancyArgs& b, hipStream_t s);
+// Prescribed boundary velocities (include/cfd2_amd.h "Arithmetic of boundary
+// velocities" is the contract), one more kernel argument of the BCV forms only:
+// the plain kernels keep their arguments.  sel[i] = 0: cell i has no selected
+// slot; else 1 + its row in the compact table, tab[row * fs.wf + k] = {bx, by,
+// kind, 0} of slot k: kind 0 not selected, 1 a selected inlet slot, 3 a selected
+// wall slot (the slot's boundary type as a float).  The table has one row per
+// cell with a selected slot, O(sqrt N) rows; it is read only inside the branch
+// of a boundary slot of such a cell.  Per selected slot
+//   g = scale * ramp (scale: inlet_scale on an inlet slot, wall_scale on a wall slot)
+//   ubx = bx * g;  uby = by * g
+// replace inlet_velocity * ramp, 0 (inlet) and 0, 0 (wall).
+struct BcvArgs {
+  const uint32_t* sel;  // [N]
+  const float4* tab;    // [rows * fs.wf]
+  float inlet_scale, wall_scale;
+};
+constexpr float kBcvInlet = 1.0f, kBcvWall = 3.0f;
+void launch_prepare_bcv(const PrepareArgs& a, const BcvArgs& v, hipStream_t s);
+// buoy: null for the form without the Boussinesq source
+void launch_assemble_bcv(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs& v, hipStream_t s);
 // writes per-block max bit patterns to blockmax[2*nb] and the final pair to maxbits[0..1]
 // (and to host_out[0..1], a device view of pinned host memory, when non-null)
 void launch_update_fields(uint32_t N, float alpha_u, float alpha_p, const float* x, float2* u,
@@ -545,6 +565,36 @@ struct FlowDiagArgs {
 };
 // maxout[0..2] = bits of max s (f64), max |omega|, max |div| (f32 bits, zero-extended)
 void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s);
+// The BCV form (BcvArgs above): the face value of a selected inlet or wall slot
+// is (ubx, uby), and the viscous force of a selected wall slot in the force
+// region is viscosity * ((double)u - (double)ubx) * area / dist_e.
+void launch_flow_diag_bcv(const FlowDiagArgs& a, const BcvArgs& v, unsigned long long* maxout, hipStream_t s);
+// Read-only wall-motion sums over the force-region wall slots (wall_mask, as
+// FlowDiagArgs): per cell, in f64, in ascending slot order, with F_p = p n area
+// and F_v = viscosity (u - ub) area / dist_e as k_flow_diag forms them and the
+// lever arm r = ctr[row * fs.wf + k] - (x0, y0) (crow[i] = 1 + row, the compact
+// table of the f64 face centres of the region's cells):
+//   0 torque of F_p: r_x F_py - r_y F_px      1 torque of F_v
+//   2 power: -((F_px + F_vx) ubx + (F_py + F_vy) uby) on a selected slot, else +0
+// Unit partials partial[f * np + unit] in the canonical tree.  v.sel null: no
+// selection (ub = 0 everywhere).
+constexpr int kWallMotionSums = 3;
+struct WallMotionArgs {
+  uint32_t N;
+  cfd_constants c;
+  FaceSlots fs;
+  const float2* u;
+  const float* p;
+  const uint16_t* wall_mask;  // [N]
+  const uint32_t* crow;       // [N]
+  const double2* ctr;         // [rows * fs.wf]
+  BcvArgs v;
+  double x0, y0;
+  uint32_t U;                 // chunks per unit (RedGeom::U)
+  uint32_t np;                // unit partials per sum
+  double* partial;            // [kWallMotionSums * np]
+};
+void launch_wall_motion(const WallMotionArgs& a, hipStream_t s);
 
 // ---- scalar.hip ----
 // Passive scalar transport (include/cfd2_amd.h, the last section): implicit

@@ -668,6 +668,32 @@ cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out) {
   return guard([&] { s->s->buoyancy_force(out); });
 }
 
+// -------------------------------------------- prescribed boundary velocities
+cfd_status cfd_set_boundary_velocity(cfd_solver* s, uint32_t n, const uint32_t* face_ids, const float* vx,
+                                     const float* vy, uint32_t* selected) {
+  CHECK_S(s);
+  if (n && (!face_ids || !vx || !vy)) return set_error(CFD_ERR_INVALID, "null face_ids / vx / vy");
+  return guard([&] {
+    const uint32_t c = s->s->set_boundary_velocity(n, face_ids, vx, vy);
+    if (selected) *selected = c;
+  });
+}
+cfd_status cfd_set_boundary_velocity_scale(cfd_solver* s, float inlet_scale, float wall_scale) {
+  CHECK_S(s);
+  return guard([&] { s->s->set_boundary_velocity_scale(inlet_scale, wall_scale); });
+}
+cfd_status cfd_boundary_velocity_get(const cfd_solver* s, cfd_boundary_velocity* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  s->s->boundary_velocity_get(out);
+  return CFD_OK;
+}
+cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_motion* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->wall_motion(x0, y0, out); });
+}
+
 // ------------------------------------------------------- frames on the device
 cfd_status cfd_render_set_polygons(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
                                    const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices) {

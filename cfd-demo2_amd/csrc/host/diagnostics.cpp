@@ -59,7 +59,10 @@ void Solver::flow_diag_device(bool fields, bool reduce) {
   a.partial = diag_partial;
   a.blockmax = diag_blockmax;
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(diag_res + 6);
-  launch_flow_diag(a, mx, stream);
+  if (bcv_on())  // prescribed boundary velocities: the moving walls' face values and relative velocity
+    launch_flow_diag_bcv(a, bcv_args(), mx, stream);
+  else
+    launch_flow_diag(a, mx, stream);
   if (!reduce) {  // derived fields only: nothing to reduce across ranks, not collective
     check_launch("flow diagnostics (fields)");
     return;
@@ -142,6 +145,8 @@ uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
       mask[wfc.cell - topo.c0] |= (uint16_t)(1u << wfc.slot);
     }
   region_faces = count;
+  ++region_gen;  // wall_motion rebuilds its table of face centres
+  region_box[0] = x0, region_box[1] = y0, region_box[2] = x1, region_box[3] = y1;
   region_on = count != 0;  // every rank runs the same kernel form (the force sums of a rank without faces are +0)
   if (!region_on) return 0;
   if (mask.empty()) mask.assign(N, 0);

@@ -61,7 +61,12 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
       if (f >= mesh.num_faces) throw std::invalid_argument("cell_faces out of range");
       if (mesh.face_neighbor[f] == UINT32_MAX && (mesh.face_boundary[f] & 3u) == 3u)
         wall_faces.push_back({mesh.face_cx[f], mesh.face_cy[f], i, k - mesh.cell_face_offsets[i]});
+      const uint32_t bt = mesh.face_boundary[f] & 3u;
+      if (R == 1 && mesh.face_neighbor[f] == UINT32_MAX && (bt == 1u || bt == 3u))  // boundary_velocity.cpp
+        bnd_faces.push_back({f, i, k - mesh.cell_face_offsets[i], bt, mesh.face_nx[f], mesh.face_ny[f],
+                             mesh.face_cx[f], mesh.face_cy[f]});
     }
+  std::sort(bnd_faces.begin(), bnd_faces.end(), [](const BndFace& a, const BndFace& b) { return a.face < b.face; });
   if (R == 1) {  // passive scalars (one GPU only): the source box tests the f64 centres
     cell_cx.assign(mesh.cell_cx, mesh.cell_cx + NG);
     cell_cy.assign(mesh.cell_cy, mesh.cell_cy + NG);
@@ -224,6 +229,8 @@ Solver::~Solver() {
   if (hev_done) (void)hipEventDestroy(hev_done);
   comm.reset();
   arena.release();
+  bcv_arena.release();
+  wm_arena.release();
   amg_arena.release();
   sc_arena.release();
   if (cstream) (void)hipStreamDestroy(cstream);
@@ -344,7 +351,10 @@ void Solver::prepare() {
     check_launch("prepare (reference semantics)");
     return;
   }
-  launch_prepare(a, stream);
+  if (bcv_on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
+    launch_prepare_bcv(a, bcv_args(), stream);
+  else
+    launch_prepare(a, stream);
   check_launch("prepare");
   // commit d_p / grad_p (snapshot semantics): swap the scratch into the slot
   std::swap(S().dp, dp_scratch);
@@ -378,7 +388,10 @@ void Solver::assemble() {
   // Boussinesq buoyancy (scalar.cpp): the buoyant form only when a field drives
   // and g != 0; otherwise the plain kernel with the arguments it always had
   BuoyancyArgs b;
-  if (buoyancy_args(b))
+  const bool buoyant = buoyancy_args(b);
+  if (bcv_on())  // prescribed boundary velocities: the BCV form of either
+    launch_assemble_bcv(a, buoyant ? &b : nullptr, bcv_args(), stream);
+  else if (buoyant)
     launch_assemble_buoyant(a, b, stream);
   else
     launch_assemble(a, stream);

@@ -676,6 +676,44 @@ struct Solver {
   bool buoyancy_args(BuoyancyArgs& b) const;
   void buoyancy_get(cfd_buoyancy* out) const;
   void buoyancy_force(cfd_buoyancy_force* out);
+  // ---- prescribed boundary velocities (boundary_velocity.cpp; kernels.hpp BcvArgs) ----
+  // Opt-in: nothing below is allocated before the first non-empty
+  // set_boundary_velocity, and with an empty selection step() launches the
+  // kernels it always launched.  One GPU only; not in reference-semantics mode.
+  struct BndFace {      // every inlet and wall face of the mesh (one GPU), ascending face index
+    uint32_t face;
+    uint32_t cell, slot;
+    uint32_t btype;     // 1 inlet, 3 wall
+    double nx, ny;      // the f64 face normal (its sign does not matter here)
+    double cx, cy;      // the f64 face centre
+  };
+  struct BcvEntry {
+    float bx, by;
+    uint32_t btype;
+  };
+  std::vector<BndFace> bnd_faces;
+  std::vector<std::pair<uint32_t, BcvEntry>> bcv_sel;  // (index into bnd_faces, entry), ascending
+  DeviceArena bcv_arena;
+  uint32_t* bcv_dsel = nullptr;   // [N]; null: empty selection
+  float4* bcv_dtab = nullptr;     // [rows * wf]
+  float bcv_scale[2] = {1.0f, 1.0f};  // inlet, wall
+  double bcv_max_normal = 0.0;    // largest |v . n| removed from a wall entry of the current selection
+  bool bcv_on() const { return bcv_dsel != nullptr; }
+  BcvArgs bcv_args() const { return BcvArgs{bcv_dsel, bcv_dtab, bcv_scale[0], bcv_scale[1]}; }
+  void bcv_need(const char* what) const;  // throws: distributed, reference semantics
+  uint32_t set_boundary_velocity(uint32_t n, const uint32_t* faces, const float* vx, const float* vy);
+  void set_boundary_velocity_scale(float inlet_scale, float wall_scale);
+  void boundary_velocity_get(cfd_boundary_velocity* out) const;
+  // wall-motion sums over the force region: the compact table of the region's
+  // f64 face centres is rebuilt when the region changed (region_gen)
+  DeviceArena wm_arena;
+  uint32_t* wm_crow = nullptr;    // [N]
+  double2* wm_ctr = nullptr;      // [rows * wf]
+  double* wm_partial = nullptr;   // [kWallMotionSums * pstride]
+  double* wm_res = nullptr;       // [kWallMotionSums]
+  uint64_t region_gen = 0, wm_gen = 0;  // set_force_region calls; the one wm_crow / wm_ctr were built for
+  double region_box[4] = {0, 0, -1, 0};
+  void wall_motion(double x0, double y0, cfd_wall_motion* out);
   // ---- frames on the device (render.cpp; kernels.hpp "render.hip") ----
   // Opt-in and read-only: nothing below is allocated before render_set_polygons,
   // and step() launches none of it.  One GPU only.  rd_arena holds what depends

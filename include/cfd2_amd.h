@@ -951,6 +951,99 @@ cfd_status cfd_buoyancy_get(const cfd_solver* s, cfd_buoyancy* out);
 cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out);
 
 /* ------------------------------------------------------------------------ */
+/* Prescribed boundary velocities: inlet profiles and moving walls.  Without
+ * them the flow has one boundary velocity, inlet_velocity * ramp along +x on
+ * every inlet face, and every wall is at rest.  cfd_set_boundary_velocity gives
+ * a chosen set of inlet (1) and wall (3) boundary faces a velocity vector of
+ * their own: a parabolic or pulsatile inlet, a rotating cylinder, a moving
+ * belt.  Opt-in: with an empty selection (the default) cfd_step launches the
+ * kernels it always launched, with the same arguments, and produces the same
+ * bits; otherwise prepare_coupled, the assembly and the flow diagnostics run in
+ * their BCV forms, which read 4 more bytes per cell and a compact table (one
+ * row per cell with a selected face, O(sqrt N) rows) inside the boundary
+ * branches only.  Walls stay impermeable: for a wall face the host removes the
+ * normal component (v . n) n / (n . n) in f64 before it rounds the vector to
+ * f32; cfd_boundary_velocity.max_normal_removed reports the largest |v . n| /
+ * |n| removed since the selection was last empty.
+ *
+ * Arithmetic of boundary velocities.  All f32, one rounding per operation
+ * (nothing fused).  For a selected slot with the uploaded (bx, by), in every
+ * kernel that uses it:
+ *   g   = scale * ramp     ramp = smoothstep(0, ramp_time, time) of the step,
+ *                          scale = inlet_scale on an inlet slot, wall_scale on
+ *                          a wall slot
+ *   ubx = bx * g;  uby = by * g
+ * prepare_coupled, selected inlet slot:
+ *   flux = density * (ubx * nfx + uby * nfy) * area      (nf: the flux normal)
+ *   face value of the velocity gradients: vfu = ubx, vfv = uby
+ * prepare_coupled, selected wall slot: flux (0) and the diagonal (+ diff_coeff)
+ *   are unchanged; vfu = ubx, vfv = uby.
+ * assembly, selected inlet slot: the plain inlet branch with this ubx, and
+ *   with uby where it has the literal 0, each operation at the slot's place in
+ *   the face loop:
+ *     diag += diff_coeff;  rhs_u += diff_coeff * ubx;  rhs_v += diff_coeff * uby
+ *     flux > 0: diag += flux;  else rhs_u -= flux * ubx;  rhs_v -= flux * uby
+ *     flux_bc = (ubx * nx + uby * ny) * area;  rhs_p -= flux_bc
+ * assembly, selected wall slot: the plain wall branch (diag += diff_coeff, the
+ *   pressure-gradient sums), then
+ *     rhs_u += diff_coeff * ubx;  rhs_v += diff_coeff * uby
+ * An unselected boundary slot keeps the plain arithmetic exactly.  d_p is
+ * unchanged: the Rhie-Chow flux does not see a wall's tangential motion.
+ * Flow diagnostics (cfd_flow_diagnostics, cfd_get_derived, the renderer's
+ * vorticity, the monitor): the face value follows prepare_coupled; the viscous
+ * force of a selected wall face of the force region is, in f64,
+ *   viscosity * ((double)u - (double)ubx) * area / dist   (and v, uby)
+ * in place of viscosity * u * area / dist.
+ * cfd_wall_motion_get: over the wall faces of the force region
+ * (cfd_set_force_region), per cell in f64 in ascending slot order, with F_p =
+ * p n area and F_v as above (the forces of the fluid on the wall, as
+ * cfd_flow_diag forms them) and r = (f64 face centre) - (x0, y0):
+ *   torque_pressure += r_x F_py - r_y F_px
+ *   torque_viscous  += r_x F_vy - r_y F_vx
+ *   power           -= (F_px + F_vx) * ubx + (F_py + F_vy) * uby   selected faces only
+ * each summed over the cells in the canonical order.  power is what the
+ * selected moving walls of the region deliver to the fluid, -sum F_on_wall .
+ * u_wall.  An empty region: zeros, nothing launched.
+ * The scales are kernel arguments of prepare_coupled and the assembly, which a
+ * step launches itself also when the Krylov iteration replays a captured graph
+ * (cfd_graph_enable): a change takes effect at the next cfd_step.
+ * Checkpoints do not store the selection or the scales (the file format and its
+ * version are unchanged): a resumed run re-applies them.  One GPU only, and not
+ * together with flag 2 of cfd_debug_reference_semantics.                     */
+typedef struct cfd_boundary_velocity {
+  uint32_t inlet_faces;      /* selected inlet faces */
+  uint32_t wall_faces;       /* selected wall faces */
+  float inlet_scale;
+  float wall_scale;
+  int32_t active;            /* 1: the next cfd_step runs the BCV forms */
+  int32_t reserved;
+  double max_normal_removed; /* largest |v . n| / |n| removed from a wall entry */
+} cfd_boundary_velocity;
+typedef struct cfd_wall_motion {
+  double torque_pressure;    /* about (x0, y0), of the pressure force of the fluid on the region's walls */
+  double torque_viscous;     /* ... of the viscous force */
+  double power;              /* delivered to the fluid by the region's selected walls */
+  uint32_t region_faces;     /* wall faces of the force region */
+  uint32_t moving_faces;     /* of these, selected ones */
+} cfd_wall_motion;
+/* face_ids: global face indices, each an inlet (1) or wall (3) boundary face;
+ * vx, vy: the f32 velocity of each.  A later entry (or call) replaces an earlier
+ * one of the same face; n == 0 clears the whole selection (the pointers may be
+ * null).  *selected (optional) = faces selected afterwards.  CFD_ERR_INVALID: a
+ * face that is no inlet or wall boundary face, a velocity that is not finite, a
+ * distributed handle, reference semantics with flag 2.  A refused call changes
+ * nothing.  Takes effect at the next cfd_step.                               */
+cfd_status cfd_set_boundary_velocity(cfd_solver* s, uint32_t n, const uint32_t* face_ids, const float* vx,
+                                     const float* vy, uint32_t* selected);
+/* Two factors (default 1, 1) applied on the device: a pulsatile inlet or an
+ * oscillating rotation needs no new upload.  They stay over a cleared selection. */
+cfd_status cfd_set_boundary_velocity_scale(cfd_solver* s, float inlet_scale, float wall_scale);
+/* The settings back; never fails on a valid handle.                          */
+cfd_status cfd_boundary_velocity_get(const cfd_solver* s, cfd_boundary_velocity* out);
+/* Read-only.  CFD_ERR_INVALID: a distributed handle, x0 or y0 not finite.     */
+cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_motion* out);
+
+/* ------------------------------------------------------------------------ */
 /* Frames on the device: a cell field as an H x W RGBA8 image, the headless
  * form of the reference's renderer (src/ui/cfd_renderer.rs fan-triangulates
  * every cell, cfd_mesh_shader.wgsl colours each fan by the cell's value).  The
