@@ -84,6 +84,14 @@ inline RedGeom red_geom(uint64_t nglob) {
   return r;
 }
 
+// Where a chunk kernel leaves the unit partials of its f64 sums (reduce_dev.hpp
+// sum_accumulate / sum_store): sum f's unit k at partial[f * np + k].
+struct SumOut {
+  uint32_t U;       // chunks per unit (RedGeom::U)
+  uint32_t np;      // unit partials per sum (the stride between sums)
+  double* partial;  // [sums * np]
+};
+
 // Source of a reduction's segment values for the kernels that finish it
 // (the total's tree).  One GPU: unit partials p[v * stride + k], k < nchunks
 // (here: units), G units per segment; the segment trees are built from them.  Distributed: the all-gathered
@@ -558,17 +566,14 @@ struct FlowDiagArgs {
   const uint16_t* wall_mask;  // [N] bit k: wall slot k is in the force region; null: no region (forces +0)
   float* omega_out;           // [N] or null (both null: the scalar-only pass)
   float* div_out;
-  uint32_t U;                 // chunks per unit (RedGeom::U)
-  uint32_t np;                // unit partials per sum
-  double* partial;            // [kFlowDiagSums * np]
+  SumOut out;                 // [kFlowDiagSums * np]
   unsigned long long* blockmax;  // [3 * red_blocks(N)] scratch
 };
 // maxout[0..2] = bits of max s (f64), max |omega|, max |div| (f32 bits, zero-extended)
-void launch_flow_diag(const FlowDiagArgs& a, unsigned long long* maxout, hipStream_t s);
-// The BCV form (BcvArgs above): the face value of a selected inlet or wall slot
-// is (ubx, uby), and the viscous force of a selected wall slot in the force
-// region is viscosity * ((double)u - (double)ubx) * area / dist_e.
-void launch_flow_diag_bcv(const FlowDiagArgs& a, const BcvArgs& v, unsigned long long* maxout, hipStream_t s);
+// v != null, the BCV form (BcvArgs above): the face value of a selected inlet or
+// wall slot is (ubx, uby), and the viscous force of a selected wall slot in the
+// force region is viscosity * ((double)u - (double)ubx) * area / dist_e.
+void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, unsigned long long* maxout, hipStream_t s);
 // Read-only wall-motion sums over the force-region wall slots (wall_mask, as
 // FlowDiagArgs): per cell, in f64, in ascending slot order, with F_p = p n area
 // and F_v = viscosity (u - ub) area / dist_e as k_flow_diag forms them and the
@@ -590,9 +595,7 @@ struct WallMotionArgs {
   const double2* ctr;         // [rows * fs.wf]
   BcvArgs v;
   double x0, y0;
-  uint32_t U;                 // chunks per unit (RedGeom::U)
-  uint32_t np;                // unit partials per sum
-  double* partial;            // [kWallMotionSums * np]
+  SumOut out;                 // [kWallMotionSums * np]
 };
 void launch_wall_motion(const WallMotionArgs& a, hipStream_t s);
 
@@ -680,9 +683,7 @@ struct ScalarWallFluxArgs {
   float rd;              // density * D
   int32_t kind;          // 1 or 2
   float value;
-  uint32_t U;            // chunks per unit (RedGeom::U)
-  uint32_t np;           // unit partials per sum
-  double* partial;       // [kWallFluxSums * np]
+  SumOut out;            // [kWallFluxSums * np]
 };
 void launch_scalar_wall_flux(const ScalarWallFluxArgs& a, hipStream_t s);
 // Read-only body-force diagnostic of the buoyancy the assembly adds (flux.hip
@@ -698,9 +699,7 @@ struct BuoyancyForceArgs {
   const float* vol;
   BuoyancyArgs b;
   float density;
-  uint32_t U;       // chunks per unit (RedGeom::U)
-  uint32_t np;      // unit partials per sum
-  double* partial;  // [kBuoyancySums * np]
+  SumOut out;  // [kBuoyancySums * np]
 };
 void launch_buoyancy_force(const BuoyancyForceArgs& a, hipStream_t s);
 // The assembled system as the solvers read it: the Jacobi row of cell i is
@@ -748,9 +747,7 @@ struct ScalarStatsArgs {
   uint32_t N;
   const float* vol;
   const float* phi;
-  uint32_t U;          // chunks per unit (RedGeom::U)
-  uint32_t np;         // unit partials
-  double* partial;     // [np]
+  SumOut out;          // [np]
   uint32_t* blockmm;   // [2 * red_blocks(N)] scratch
 };
 void launch_scalar_stats(const ScalarStatsArgs& a, ScalarResults* res, hipStream_t s);
@@ -776,9 +773,7 @@ struct ScalarKrylovArgs {
   ScalarSystem sys;
   float* x;               // [N] phi_old on entry, the frozen iterate after the stop
   float *rh, *r, *p, *v, *s, *t;  // [N] work vectors
-  uint32_t U;             // chunks per unit (RedGeom::U)
-  uint32_t np;            // unit partials per dot
-  double* partial;        // [2 * np]
+  SumOut out;             // [2 * np]
   uint32_t* blockmax;     // [red_blocks(N)]
   ScalarKrylovState* state;
   RedSrcD red;           // combine(partial, 2)

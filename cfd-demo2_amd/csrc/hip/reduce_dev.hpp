@@ -268,6 +268,46 @@ __device__ __forceinline__ void unit_partials(const double (*l)[4], uint32_t U, 
   const double v = unit_value(ch, U, u);
   if ((uint64_t)unit * U * kRedChunkCells < N && unit < np) dst[unit] = v;
 }
+// ---- the block skeleton of every kernel with f64 cell sums ----
+// Block lb of such a kernel takes kRedBlockCells cells (kernels.hpp): chunk q is
+// its 256 cells of round q, wavefront w the chunk's quarter w.  A kernel keeps
+// `__shared__ double lsum[NS][4][4]` ([sum][chunk q][quarter w]), calls
+// sum_accumulate with its per-cell term, folds its maxima (if any) into LDS of
+// its own, and after one __syncthreads() calls sum_store: every sum it writes
+// has the bits of the canonical tree.
+//
+// The accumulate half (no barrier): per round, t[0, NS) from +0, term(i, t) for
+// a cell inside the mesh, then the quarter's shuffle tree of each sum.  Only
+// the first LIVE sums are reduced; the others are +0 whatever term left in them.
+template <int NS, int LIVE = NS, class Term>
+__device__ __forceinline__ void sum_accumulate(double (*lsum)[4][4], uint32_t N, uint32_t lb, Term term) {
+  const uint32_t w = threadIdx.x >> 6, lane = red_lane();
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
+    double t[NS];
+#pragma unroll
+    for (int f = 0; f < NS; ++f) t[f] = 0.0;
+    if (ci < N) term((uint32_t)ci, t);
+#pragma unroll
+    for (int f = 0; f < LIVE; ++f) {
+      const double r = wave_tree(t[f]);
+      if (lane == 0) lsum[f][q][w] = r;
+    }
+    if constexpr (LIVE < NS) {
+      if (lane == 0) {
+#pragma unroll
+        for (int f = LIVE; f < NS; ++f) lsum[f][q][w] = 0.0;
+      }
+    }
+  }
+}
+// The store half (after the barrier): thread f UB + u, UB = 4 / U units per
+// block, stores unit u of sum f to o.partial[f * np + unit] (unit_partials).
+template <int NS>
+__device__ __forceinline__ void sum_store(const double (*lsum)[4][4], const SumOut& o, uint32_t N, uint32_t lb) {
+  const uint32_t UB = 4 / o.U, f = threadIdx.x / UB;
+  if (f < NS) unit_partials(lsum[f], o.U, o.np, N, lb, o.partial + (size_t)f * o.np, threadIdx.x % UB);
+}
 // the block's chunks are all inside the mesh
 __device__ __forceinline__ bool block_full(uint32_t N, uint32_t b = ~0u) {
   return (size_t)((b == ~0u ? blockIdx.x : b) + 1) * kRedBlockCells <= N;

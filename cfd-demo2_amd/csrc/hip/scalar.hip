@@ -13,8 +13,9 @@
 //                 and the wall-flux sums)
 //   scalar_row    the Jacobi row sum of kernels.hpp ScalarSystem (the sweep
 //                 and the BiCGStab operator)
-//   reduce_dev.hpp: unit_partials (a block's sums), wave_max / block_of4_max
-//                 (its maxima), k_block_fold (the maxima of all blocks)
+//   reduce_dev.hpp: sum_accumulate / sum_store (a block's f64 sums), wave_max /
+//                 block_of4_max (its maxima), k_block_fold (the maxima of all
+//                 blocks)
 // The sweep and the pointwise kernels run thread per cell (row_id); the kernels
 // that sum run over blocks of kRedBlockCells cells, chunk by chunk.
 #include <hip/hip_runtime.h>
@@ -334,30 +335,24 @@ __global__ void __launch_bounds__(kBlock) k_scalar_sweep(ScalarSweepArgs a) {
   }
 }
 
-// Field statistics, the shape of k_flow_diag: blocks of kRedBlockCells cells;
-// the sum's tree is the quarter's shuffle tree, then unit_partials.
+// Field statistics: the integral over the shared skeleton (reduce_dev.hpp
+// sum_accumulate / sum_store), the minimum and maximum as keys.
 __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
-  __shared__ double lsum[4][4];  // [chunk q][quarter w]
+  __shared__ double lsum[1][4][4];  // [sum][chunk q][quarter w]
   __shared__ uint32_t lmm[2][4];
   const uint32_t N = a.N;
   const uint32_t lb = xcd_block();
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint32_t kmin = ~0u, kmax = 0u;
-  for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
-    double t = 0.0;
-    if (ci < N) {
-      const float ph = a.phi[ci];
-      t = (double)a.vol[ci] * (double)ph;
-      if (ph == ph) {
-        const uint32_t key = scalar_value_key(__float_as_uint(ph));
-        kmin = key < kmin ? key : kmin;
-        kmax = key > kmax ? key : kmax;
-      }
+  sum_accumulate<1>(lsum, N, lb, [&](uint32_t ci, double* t) {
+    const float ph = a.phi[ci];
+    t[0] = (double)a.vol[ci] * (double)ph;
+    if (ph == ph) {
+      const uint32_t key = scalar_value_key(__float_as_uint(ph));
+      kmin = key < kmin ? key : kmin;
+      kmax = key > kmax ? key : kmax;
     }
-    const double r = wave_tree(t);
-    if (lane == 0) lsum[q][w] = r;
-  }
+  });
   kmin = wave_min(kmin);
   kmax = wave_max(kmax);
   if (lane == 0) {
@@ -365,86 +360,63 @@ __global__ void __launch_bounds__(kBlock) k_scalar_stats(ScalarStatsArgs a) {
     lmm[1][w] = kmax;
   }
   __syncthreads();
-  unit_partials(lsum, a.U, a.np, N, lb, a.partial);
+  sum_store<1>(lsum, a.out, N, lb);
   if (threadIdx.x == 64) {
     a.blockmm[2 * (size_t)lb] = block_of4_min(lmm[0]);
     a.blockmm[2 * (size_t)lb + 1] = block_of4_max(lmm[1]);
   }
 }
 
-// The wall-flux sums (kernels.hpp ScalarWallFluxArgs), the shape of
-// k_scalar_stats: a cell with a selected slot walks the set bits of its image
-// word in ascending order, every other cell loads that word alone.  Read-only.
+// The wall-flux sums (kernels.hpp ScalarWallFluxArgs) over the shared skeleton:
+// a cell with a selected slot walks the set bits of its image word in
+// ascending order, every other cell loads that word alone.  Read-only.
 __global__ void __launch_bounds__(kBlock) k_scalar_wall_flux(ScalarWallFluxArgs a) {
   __shared__ double lsum[kWallFluxSums][4][4];  // [sum][chunk q][quarter w]
   const uint32_t N = a.N;
   const uint32_t lb = xcd_block();
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
-    double t[kWallFluxSums] = {0.0, 0.0, 0.0};
-    if (ci < N) {
-      const uint32_t i = (uint32_t)ci;
-      uint32_t walls = a.sel[i] & kSelWalls;
-      if (walls) {
-        const double ph = (double)a.phi[i];
-        while (walls) {
-          const uint32_t k = (uint32_t)__ffs((int)walls) - 1u;
-          walls &= walls - 1u;
-          const size_t e = (size_t)k * N + i;
-          const float area = a.area[e];
-          if (a.kind == 1)
-            t[0] += (double)scalar_wall_coef(a.rd, area, a.dist_e[e]) * ((double)a.value - ph);
-          else
-            t[0] += (double)a.value * (double)area;
-          t[1] += (double)area;
-          t[2] += (double)area * ph;
-        }
+  sum_accumulate<kWallFluxSums>(lsum, N, lb, [&](uint32_t i, double* t) {
+    uint32_t walls = a.sel[i] & kSelWalls;
+    if (walls) {
+      const double ph = (double)a.phi[i];
+      while (walls) {
+        const uint32_t k = (uint32_t)__ffs((int)walls) - 1u;
+        walls &= walls - 1u;
+        const size_t e = (size_t)k * N + i;
+        const float area = a.area[e];
+        if (a.kind == 1)
+          t[0] += (double)scalar_wall_coef(a.rd, area, a.dist_e[e]) * ((double)a.value - ph);
+        else
+          t[0] += (double)a.value * (double)area;
+        t[1] += (double)area;
+        t[2] += (double)area * ph;
       }
     }
-#pragma unroll
-    for (int f = 0; f < kWallFluxSums; ++f) {
-      const double r = wave_tree(t[f]);
-      if (lane == 0) lsum[f][q][w] = r;
-    }
-  }
+  });
   __syncthreads();
-  const uint32_t UB = 4 / a.U, f = threadIdx.x / UB;  // thread f UB + u: unit u of sum f
-  if (f < kWallFluxSums) unit_partials(lsum[f], a.U, a.np, N, lb, a.partial + (size_t)f * a.np, threadIdx.x % UB);
+  sum_store<kWallFluxSums>(lsum, a.out, N, lb);
 }
 
-// The buoyancy body force (kernels.hpp BuoyancyForceArgs), the shape of
-// k_scalar_stats with two sums: per cell one 4-byte load per driving field and
-// the volume.  Read-only.
+// The buoyancy body force (kernels.hpp BuoyancyForceArgs), two sums over the
+// shared skeleton: per cell one 4-byte load per driving field and the volume.
+// Read-only.
 __global__ void __launch_bounds__(kBlock) k_buoyancy_force(BuoyancyForceArgs a) {
   __shared__ double lsum[kBuoyancySums][4][4];  // [component][chunk q][quarter w]
   const uint32_t N = a.N;
   const uint32_t lb = xcd_block();
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double gx = (double)a.b.gx, gy = (double)a.b.gy;
-  for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
-    double t[kBuoyancySums] = {0.0, 0.0};
-    if (ci < N) {
-      const double vr = (double)a.vol[ci] * (double)a.density;
+  sum_accumulate<kBuoyancySums>(lsum, N, lb, [&](uint32_t ci, double* t) {
+    const double vr = (double)a.vol[ci] * (double)a.density;
 #pragma unroll
-      for (int f = 0; f < kMaxBuoyancyFields; ++f) {  // unrolled: every entry a fixed kernel-argument offset
-        if (f < a.b.n) {
-          const double m = (vr * (double)a.b.f[f].beta) * ((double)a.b.f[f].phi[ci] - (double)a.b.f[f].ref);
-          t[0] = t[0] - m * gx;
-          t[1] = t[1] - m * gy;
-        }
+    for (int f = 0; f < kMaxBuoyancyFields; ++f) {  // unrolled: every entry a fixed kernel-argument offset
+      if (f < a.b.n) {
+        const double m = (vr * (double)a.b.f[f].beta) * ((double)a.b.f[f].phi[ci] - (double)a.b.f[f].ref);
+        t[0] = t[0] - m * gx;
+        t[1] = t[1] - m * gy;
       }
     }
-#pragma unroll
-    for (int c = 0; c < kBuoyancySums; ++c) {
-      const double r = wave_tree(t[c]);
-      if (lane == 0) lsum[c][q][w] = r;
-    }
-  }
+  });
   __syncthreads();
-  const uint32_t UB = 4 / a.U, c = threadIdx.x / UB;  // thread c UB + u: unit u of component c
-  if (c < kBuoyancySums) unit_partials(lsum[c], a.U, a.np, N, lb, a.partial + (size_t)c * a.np, threadIdx.x % UB);
+  sum_store<kBuoyancySums>(lsum, a.out, N, lb);
 }
 
 // ---- BiCGStab on the Jacobi-scaled system (kernels.hpp ScalarKrylovArgs) ----
@@ -462,54 +434,42 @@ constexpr int kKryInit = 0, kKryV = 1, kKryT = 2;
 // <t, t>.  A p = p - J0(p), J0 = scalar_row from 0 over the diagonal.
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_op(ScalarKrylovArgs a) {
-  __shared__ double lsum[2][4][4];  // [dot][chunk q][quarter w]
+  constexpr int ND = MODE == kKryT ? 2 : 1;
+  __shared__ double lsum[ND][4][4];  // [dot][chunk q][quarter w]
   __shared__ uint32_t lmax[kBlock / 64];
   if (MODE != kKryInit && a.state->st[kKryDone]) return;
   const ScalarSystem& m = a.sys;
   const uint32_t N = m.N;
   const uint32_t lb = xcd_block();
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float* __restrict__ in = MODE == kKryInit ? a.x : (MODE == kKryV ? a.p : a.s);
   float* __restrict__ out = MODE == kKryInit ? a.r : (MODE == kKryV ? a.v : a.t);
   uint32_t bits = 0;
-  for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
-    double t0 = 0.0, t1 = 0.0;
-    if (ci < N) {
-      const uint32_t i = (uint32_t)ci;
-      const float sum0 = MODE == kKryInit ? ldx<kKryNT>(m.b + i) : 0.0f;
-      const float dg = ldx<kKryNT>(m.diag + i);
-      const float qd = scalar_row<kKryNT>(m.other, m.coef, N, m.ld, m.nface[i], i, in, sum0) / dg;
-      const float own = in[i];
-      const float res = MODE == kKryInit ? qd - own : own - qd;
-      out[i] = res;
-      if constexpr (MODE == kKryInit) {
-        a.rh[i] = res;
-        a.p[i] = res;
-        t0 = (double)res * (double)res;
-        const uint32_t ab = abs_bits(res);
-        bits = ab > bits ? ab : bits;
-      } else if constexpr (MODE == kKryV) {
-        t0 = (double)a.rh[i] * (double)res;
-      } else {
-        t0 = (double)res * (double)own;
-        t1 = (double)res * (double)res;
-      }
+  sum_accumulate<ND>(lsum, N, lb, [&](uint32_t i, double* t) {
+    const float sum0 = MODE == kKryInit ? ldx<kKryNT>(m.b + i) : 0.0f;
+    const float dg = ldx<kKryNT>(m.diag + i);
+    const float qd = scalar_row<kKryNT>(m.other, m.coef, N, m.ld, m.nface[i], i, in, sum0) / dg;
+    const float own = in[i];
+    const float res = MODE == kKryInit ? qd - own : own - qd;
+    out[i] = res;
+    if constexpr (MODE == kKryInit) {
+      a.rh[i] = res;
+      a.p[i] = res;
+      t[0] = (double)res * (double)res;
+      const uint32_t ab = abs_bits(res);
+      bits = ab > bits ? ab : bits;
+    } else if constexpr (MODE == kKryV) {
+      t[0] = (double)a.rh[i] * (double)res;
+    } else {
+      t[0] = (double)res * (double)own;
+      t[1] = (double)res * (double)res;
     }
-    const double r0 = wave_tree(t0);
-    if (lane == 0) lsum[0][q][w] = r0;
-    if constexpr (MODE == kKryT) {
-      const double r1 = wave_tree(t1);
-      if (lane == 0) lsum[1][q][w] = r1;
-    }
-  }
+  });
   if constexpr (MODE == kKryInit) {
     bits = wave_max(bits);
-    if (lane == 0) lmax[w] = bits;
+    if (red_lane() == 0) lmax[threadIdx.x >> 6] = bits;
   }
   __syncthreads();
-  unit_partials(lsum[0], a.U, a.np, N, lb, a.partial);
-  if constexpr (MODE == kKryT) unit_partials(lsum[1], a.U, a.np, N, lb, a.partial + a.np);
+  sum_store<ND>(lsum, a.out, N, lb);
   if constexpr (MODE == kKryInit) {
     if (threadIdx.x == 64) a.blockmax[lb] = block_of4_max(lmax);
   }
@@ -527,40 +487,32 @@ __global__ void __launch_bounds__(kBlock) k_scalar_krylov_s(ScalarKrylovArgs a) 
 // mode 0: x = (x + alpha p) + omega s, r = s - omega t; mode 1 (<t, t> == 0):
 // x = x + alpha p, r = s; mode 2: nothing.  With <rh, r> and the block maxima of |r|.
 __global__ void __launch_bounds__(kBlock) k_scalar_krylov_xr(ScalarKrylovArgs a) {
-  __shared__ double lsum[4][4];
+  __shared__ double lsum[1][4][4];  // [dot][chunk q][quarter w]
   __shared__ uint32_t lmax[kBlock / 64];
   const uint32_t mode = a.state->st[kKryMode];
   if (mode == 2u) return;
   const uint32_t N = a.sys.N;
   const uint32_t lb = xcd_block();
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float alpha = a.state->co[0], omega = a.state->co[1];
   uint32_t bits = 0;
-  for (uint32_t q = 0; q < 4; ++q) {
-    const uint64_t ci = (uint64_t)lb * kRedBlockCells + q * kRedChunkCells + threadIdx.x;
-    double t0 = 0.0;
-    if (ci < N) {
-      const uint32_t i = (uint32_t)ci;
-      const float si = a.s[i];
-      float xn = a.x[i] + alpha * a.p[i];
-      float rn = si;
-      if (mode == 0u) {
-        xn = xn + omega * si;
-        rn = si - omega * a.t[i];
-      }
-      a.x[i] = xn;
-      a.r[i] = rn;
-      t0 = (double)a.rh[i] * (double)rn;
-      const uint32_t ab = abs_bits(rn);
-      bits = ab > bits ? ab : bits;
+  sum_accumulate<1>(lsum, N, lb, [&](uint32_t i, double* t) {
+    const float si = a.s[i];
+    float xn = a.x[i] + alpha * a.p[i];
+    float rn = si;
+    if (mode == 0u) {
+      xn = xn + omega * si;
+      rn = si - omega * a.t[i];
     }
-    const double r0 = wave_tree(t0);
-    if (lane == 0) lsum[q][w] = r0;
-  }
+    a.x[i] = xn;
+    a.r[i] = rn;
+    t[0] = (double)a.rh[i] * (double)rn;
+    const uint32_t ab = abs_bits(rn);
+    bits = ab > bits ? ab : bits;
+  });
   bits = wave_max(bits);
-  if (lane == 0) lmax[w] = bits;
+  if (red_lane() == 0) lmax[threadIdx.x >> 6] = bits;
   __syncthreads();
-  unit_partials(lsum, a.U, a.np, N, lb, a.partial);
+  sum_store<1>(lsum, a.out, N, lb);
   if (threadIdx.x == 64) a.blockmax[lb] = block_of4_max(lmax);
 }
 

@@ -127,6 +127,7 @@ void Solver::wall_motion(double x0, double y0, cfd_wall_motion* out) {
     sync();
     wm_arena.release();
     wm_crow = nullptr;
+    wm_sums = SumBuf{};
     std::vector<uint32_t> crow(N, 0u);
     std::vector<double2> ctr;
     for (const WallFace& wfc : wall_faces) {
@@ -141,8 +142,6 @@ void Solver::wall_motion(double x0, double y0, cfd_wall_motion* out) {
     }
     uint32_t* dcrow = wm_arena.upload(crow, stream);
     wm_ctr = wm_arena.upload(ctr, stream);
-    wm_partial = wm_arena.alloc<double>((size_t)kWallMotionSums * pstride);
-    wm_res = wm_arena.alloc<double>(kWallMotionSums);
     sync();
     wm_crow = dcrow;
     wm_gen = region_gen;
@@ -159,15 +158,10 @@ void Solver::wall_motion(double x0, double y0, cfd_wall_motion* out) {
   a.v = bcv_on() ? bcv_args() : BcvArgs{nullptr, nullptr, bcv_scale[0], bcv_scale[1]};
   a.x0 = x0;
   a.y0 = y0;
-  a.U = red.U;
-  a.np = pstride;
-  a.partial = wm_partial;
+  a.out = sum_buf(wm_sums, kWallMotionSums, wm_arena);
   launch_wall_motion(a, stream);
-  launch_evolution_final(combine(wm_partial, kWallMotionSums), wm_res, stream);
-  check_launch("wall motion");
   double h[kWallMotionSums];
-  CFD_HIP(hipMemcpyAsync(h, wm_res, sizeof(h), hipMemcpyDeviceToHost, stream));
-  sync();
+  sum_read(wm_sums, kWallMotionSums, h, "wall motion");
   out->torque_pressure = h[0];
   out->torque_viscous = h[1];
   out->power = h[2];

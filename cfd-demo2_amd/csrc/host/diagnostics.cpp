@@ -54,15 +54,12 @@ void Solver::flow_diag_device(bool fields, bool reduce) {
   a.wall_mask = region_on ? diag_mask : nullptr;
   a.omega_out = fields ? diag_omega : nullptr;
   a.div_out = fields ? diag_div : nullptr;
-  a.U = red.U;
-  a.np = pstride;
-  a.partial = diag_partial;
+  a.out = sum_out(diag_partial);
   a.blockmax = diag_blockmax;
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(diag_res + 6);
-  if (bcv_on())  // prescribed boundary velocities: the moving walls' face values and relative velocity
-    launch_flow_diag_bcv(a, bcv_args(), mx, stream);
-  else
-    launch_flow_diag(a, mx, stream);
+  // prescribed boundary velocities: the moving walls' face values and relative velocity
+  const BcvArgs bcv = bcv_args();
+  launch_flow_diag(a, bcv_on() ? &bcv : nullptr, mx, stream);
   if (!reduce) {  // derived fields only: nothing to reduce across ranks, not collective
     check_launch("flow diagnostics (fields)");
     return;

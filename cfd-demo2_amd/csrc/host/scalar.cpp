@@ -37,8 +37,7 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   kr_state = nullptr;
   hr_grad = nullptr;
   hr_count = nullptr;
-  wf_partial = wf_res = nullptr;
-  bf_partial = bf_res = nullptr;
+  wf_sums = bf_sums = SumBuf{};
   for (ScalarField& f : sc_field) f = ScalarField{};  // every beta back to 0: the step is the plain one again
   if (count == 0) return;
   const size_t ld = topo.ld;
@@ -198,9 +197,7 @@ void Solver::scalar_krylov(ScalarField& f) {
   K.v = kr_vec[3];
   K.s = kr_vec[4];
   K.t = kr_vec[5];
-  K.U = red.U;
-  K.np = pstride;
-  K.partial = kr_partial;
+  K.out = sum_out(kr_partial);
   K.blockmax = sc_blockmax;
   K.state = kr_state;
   K.red = combine(kr_partial, 2);
@@ -335,10 +332,6 @@ void Solver::scalar_wall_flux(int field, cfd_scalar_wall_flux* out) {
   out->kind = f.wall.kind;
   if (!f.wall_on()) return;
   CFD_HIP(hipSetDevice(device));
-  if (!wf_partial) {
-    wf_partial = sc_arena.alloc<double>((size_t)kWallFluxSums * pstride);
-    wf_res = sc_arena.alloc<double>(kWallFluxSums);
-  }
   ScalarWallFluxArgs a{};
   a.N = N;
   a.area = fs.area;
@@ -348,15 +341,10 @@ void Solver::scalar_wall_flux(int field, cfd_scalar_wall_flux* out) {
   a.rd = constants.density * f.par.diffusivity;
   a.kind = f.wall.kind;
   a.value = f.wall.value;
-  a.U = red.U;
-  a.np = pstride;
-  a.partial = wf_partial;
+  a.out = sum_buf(wf_sums, kWallFluxSums, sc_arena);
   launch_scalar_wall_flux(a, stream);
-  launch_evolution_final(combine(wf_partial, kWallFluxSums), wf_res, stream);
-  check_launch("scalar wall flux");
   double h[kWallFluxSums];
-  CFD_HIP(hipMemcpyAsync(h, wf_res, sizeof(h), hipMemcpyDeviceToHost, stream));
-  sync();
+  sum_read(wf_sums, kWallFluxSums, h, "scalar wall flux");
   out->flux = h[0];
   out->area = h[1];
   out->phi_area = h[2];
@@ -415,22 +403,13 @@ void Solver::buoyancy_force(cfd_buoyancy_force* out) {
   out->fields = (uint32_t)a.b.n;
   if (!on) return;
   CFD_HIP(hipSetDevice(device));
-  if (!bf_partial) {
-    bf_partial = sc_arena.alloc<double>((size_t)kBuoyancySums * pstride);
-    bf_res = sc_arena.alloc<double>(kBuoyancySums);
-  }
   a.N = N;
   a.vol = d_vol;
   a.density = constants.density;
-  a.U = red.U;
-  a.np = pstride;
-  a.partial = bf_partial;
+  a.out = sum_buf(bf_sums, kBuoyancySums, sc_arena);
   launch_buoyancy_force(a, stream);
-  launch_evolution_final(combine(bf_partial, kBuoyancySums), bf_res, stream);
-  check_launch("buoyancy force");
   double h[kBuoyancySums];
-  CFD_HIP(hipMemcpyAsync(h, bf_res, sizeof(h), hipMemcpyDeviceToHost, stream));
-  sync();
+  sum_read(bf_sums, kBuoyancySums, h, "buoyancy force");
   out->force[0] = h[0];
   out->force[1] = h[1];
 }
@@ -443,9 +422,7 @@ void Solver::scalar_stats(int field, cfd_scalar_stats* out) {
   a.N = N;
   a.vol = d_vol;
   a.phi = f.phi;
-  a.U = red.U;
-  a.np = pstride;
-  a.partial = sc_partial;
+  a.out = sum_out(sc_partial);
   a.blockmm = sc_blockmax;
   launch_scalar_stats(a, sc_res, stream);
   launch_evolution_final(combine(sc_partial, 1), &sc_res->integral, stream);

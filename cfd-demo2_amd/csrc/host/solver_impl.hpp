@@ -462,6 +462,29 @@ struct Solver {
   // FGMRES iteration's for float, check_evolution's 5 vectors for double)
   template <class T>
   RedSrcT<T> combine(const T* part, int nvec, T* local = nullptr, T* gather = nullptr);
+  // where a kernel with f64 cell sums leaves its unit partials (kernels.hpp SumOut)
+  SumOut sum_out(double* partial) const { return SumOut{red.U, pstride, partial}; }
+  // The work space of a read-only diagnostic with ns such sums (one GPU): the
+  // unit partials and the ns totals, null before the first use.  sum_buf
+  // allocates them in `a` then and returns the kernel's destination; sum_read
+  // finishes the totals and reads them back into h[0, ns).
+  struct SumBuf {
+    double* partial = nullptr;  // [ns * pstride]
+    double* res = nullptr;      // [ns]
+  };
+  SumOut sum_buf(SumBuf& b, int ns, DeviceArena& a) {
+    if (!b.partial) {
+      b.partial = a.alloc<double>((size_t)ns * pstride);
+      b.res = a.alloc<double>(ns);
+    }
+    return sum_out(b.partial);
+  }
+  void sum_read(const SumBuf& b, int ns, double* h, const char* where) {
+    launch_evolution_final(combine(b.partial, ns), b.res, stream);
+    check_launch(where);
+    CFD_HIP(hipMemcpyAsync(h, b.res, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sync();
+  }
   std::vector<uint64_t> allgather_u64(uint64_t mine);  // every rank's value (collective)
   // ---- timing of the distributed communication (cfd_comm_timing) ----
   // While comm_prof is on, every halo exchange and all-gather of the step is
@@ -640,14 +663,11 @@ struct Solver {
   // set_scalar_scheme that selects it (null before)
   float2* hr_grad = nullptr;       // [ld] the gradient of the phi_old being advanced
   uint32_t* hr_count = nullptr;    // [4] clamped cells of each field's last scheme-1 assembly
-  // Wall-flux work space, allocated in sc_arena by the first scalar_wall_flux
-  // that has faces to sum over (null before)
-  double* wf_partial = nullptr;    // [kWallFluxSums * pstride] unit partials
-  double* wf_res = nullptr;        // [kWallFluxSums] flux, area, phi_area
-  // Buoyancy-force work space, allocated in sc_arena by the first
-  // buoyancy_force with buoyancy on (null before)
-  double* bf_partial = nullptr;    // [kBuoyancySums * pstride] unit partials
-  double* bf_res = nullptr;        // [kBuoyancySums]
+  // Wall-flux and buoyancy-force work space, allocated in sc_arena by the
+  // first scalar_wall_flux that has faces to sum over and the first
+  // buoyancy_force with buoyancy on
+  SumBuf wf_sums;                  // kWallFluxSums: flux, area, phi_area
+  SumBuf bf_sums;                  // kBuoyancySums
   float gravity[2] = {0.0f, 0.0f}; // set_gravity; kept over scalars_enable (every beta is not)
   std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: the source box)
   float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
@@ -709,8 +729,7 @@ struct Solver {
   DeviceArena wm_arena;
   uint32_t* wm_crow = nullptr;    // [N]
   double2* wm_ctr = nullptr;      // [rows * wf]
-  double* wm_partial = nullptr;   // [kWallMotionSums * pstride]
-  double* wm_res = nullptr;       // [kWallMotionSums]
+  SumBuf wm_sums;                 // kWallMotionSums, in wm_arena
   uint64_t region_gen = 0, wm_gen = 0;  // set_force_region calls; the one wm_crow / wm_ctr were built for
   double region_box[4] = {0, 0, -1, 0};
   void wall_motion(double x0, double y0, cfd_wall_motion* out);
