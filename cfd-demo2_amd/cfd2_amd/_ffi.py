@@ -337,6 +337,11 @@ class TstatsConfig(C.Structure):  # cfd_tstats_config
     _fields_ = [("second_moments", C.c_int32), ("scalars", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class SurfaceInfo(C.Structure):  # cfd_surface_info
+    _fields_ = [("faces", C.c_uint32), ("channels", C.c_uint32), ("samples", C.c_uint64), ("total_weight", C.c_double),
+                ("stats_on", C.c_int32), ("reserved", C.c_int32)]
+
+
 # cfd_tstats_get's kind argument (CFD_TSTATS_* of include/cfd2_amd.h) by name
 TSTATS_KINDS = {"u": 0, "v": 1, "p": 2, "uu": 3, "uv": 4, "vv": 5, "pp": 6, "phi": 7, "phiphi": 8, "uphi": 9, "vphi": 10}
 
@@ -402,6 +407,8 @@ EXPORTED = [
     "cfd_tstats_get", "cfd_tstats_raw_get", "cfd_tstats_raw_set", "cfd_tstats_raw_set_totals",
     "cfd_monitor_enable", "cfd_monitor_disable", "cfd_monitor_record", "cfd_monitor_count", "cfd_monitor_info",
     "cfd_monitor_get",
+    "cfd_surface_select", "cfd_surface_geometry_get", "cfd_surface_info_get", "cfd_surface_sample",
+    "cfd_surface_stats_enable", "cfd_surface_stats_reset", "cfd_surface_stats_accumulate", "cfd_surface_stats_get",
 ]
 
 _lib = None

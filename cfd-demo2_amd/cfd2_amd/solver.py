@@ -175,6 +175,14 @@ def _bind():
     L.cfd_monitor_count.argtypes = [_vp, u64p, u64p]
     L.cfd_monitor_info.argtypes = [_vp, u32p, u32p, u32p, C.POINTER(C.c_int32)]
     L.cfd_monitor_get.argtypes = [_vp, C.c_uint64, C.c_uint64, fp, fp, fp, C.POINTER(_ffi.FlowDiag)]
+    L.cfd_surface_select.argtypes = [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32)]
+    L.cfd_surface_geometry_get.argtypes = [_vp, u32p, u32p, dp, dp, dp, dp, dp, dp]
+    L.cfd_surface_info_get.argtypes = [_vp, C.POINTER(_ffi.SurfaceInfo)]
+    L.cfd_surface_sample.argtypes = [_vp, dp]
+    L.cfd_surface_stats_enable.argtypes = [_vp, C.c_int32]
+    L.cfd_surface_stats_reset.argtypes = [_vp]
+    L.cfd_surface_stats_accumulate.argtypes = [_vp, C.c_double]
+    L.cfd_surface_stats_get.argtypes = [_vp, C.c_int32, dp]
     _bound = True
     return L
 
@@ -873,6 +881,80 @@ class GpuSolver:
             self._call("cfd_tstats_raw_set", q, planes[q].ctypes.data_as(C.POINTER(C.c_double)))
         self._call("cfd_tstats_raw_set_totals", int(d["samples"]), float(d["total_weight"]))
 
+    # -- wall surface distributions: pressure, shear and heat flux per wall face ------
+    def select_surface(self, box) -> int:
+        """cfd_surface_select: the wall faces whose centre lies in the closed box
+        ``(x0, y0, x1, y1)`` (set_force_region's rule), ordered by cell, then
+        slot; returns their number.  ``x1 < x0`` clears the surface.  A second
+        call replaces the surface and resets its statistics."""
+        x0, y0, x1, y1 = (float(v) for v in box)
+        n = C.c_int32()
+        self._call("cfd_surface_select", x0, y0, x1, y1, C.byref(n))
+        return int(n.value)
+
+    def surface_info(self) -> dict:
+        """cfd_surface_info_get: ``faces``, ``channels``, ``samples``,
+        ``total_weight`` and ``stats_on``."""
+        d = _ffi.SurfaceInfo()
+        self._call("cfd_surface_info_get", C.byref(d))
+        return dict(faces=int(d.faces), channels=int(d.channels), samples=int(d.samples),
+                    total_weight=float(d.total_weight), stats_on=bool(d.stats_on))
+
+    def surface_geometry(self) -> dict:
+        """cfd_surface_geometry_get: per face ``cell``, ``slot``, the float64 face
+        centre ``cx``, ``cy`` the selection tested, and the float32 ``nx``,
+        ``ny`` (out of the cell), ``area``, ``dist_e`` the channels use, widened."""
+        n = self.surface_info()["faces"]
+        g = dict(cell=np.zeros(n, np.uint32), slot=np.zeros(n, np.uint32))
+        for k in ("cx", "cy", "nx", "ny", "area", "dist_e"):
+            g[k] = np.zeros(n)
+        u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        self._call("cfd_surface_geometry_get", g["cell"].ctypes.data_as(u32p), g["slot"].ctypes.data_as(u32p),
+                   *(g[k].ctypes.data_as(dp) for k in ("cx", "cy", "nx", "ny", "area", "dist_e")))
+        return g
+
+    @staticmethod
+    def _surface_dict(ch) -> dict:
+        nf = (len(ch) - 5) // 2
+        return dict(p=ch[0], force_p=np.stack([ch[1], ch[2]], 1), force_v=np.stack([ch[3], ch[4]], 1),
+                    flux=[ch[5 + 2 * f] for f in range(nf)], phi=[ch[6 + 2 * f] for f in range(nf)], channels=ch)
+
+    def _surface_read(self, name, *args) -> dict:
+        info = self.surface_info()
+        ch = np.zeros((info["channels"], info["faces"]))
+        self._call(name, *args, ch.ctypes.data_as(C.POINTER(C.c_double)))
+        return self._surface_dict(ch)
+
+    def surface(self) -> dict:
+        """cfd_surface_sample: the float64 channels of the current state, per face:
+        ``p``, ``force_p`` (n, 2) and ``force_v`` (n, 2), the pressure and viscous
+        force of the fluid on the face (the terms of flow_diagnostics' sums), and
+        per scalar field ``flux[f]`` (the term of scalar_wall_flux's sum) and
+        ``phi[f]``; ``channels`` holds them all, (5 + 2 fields, n)."""
+        return self._surface_read("cfd_surface_sample")
+
+    def enable_surface_stats(self, on=True) -> None:
+        """cfd_surface_stats_enable: running mean and variance of every channel."""
+        self._call("cfd_surface_stats_enable", 1 if on else 0)
+
+    def reset_surface_stats(self) -> None:
+        self._call("cfd_surface_stats_reset")
+
+    def accumulate_surface_stats(self, weight=None) -> None:
+        """cfd_surface_stats_accumulate: the current state's channels enter the
+        statistics with ``weight`` (None: the dt of the last step).  Asynchronous."""
+        self._call("cfd_surface_stats_accumulate", 0.0 if weight is None else float(weight))
+
+    def surface_stats(self, kind="mean") -> dict:
+        """cfd_surface_stats_get: ``surface()``'s layout holding the ``"mean"`` (0)
+        or the ``"variance"`` (1) of every channel."""
+        kinds = {"mean": 0, "variance": 1}
+        if isinstance(kind, str):
+            if kind not in kinds:
+                raise ValueError(f"surface_stats: unknown kind {kind!r} (one of {', '.join(kinds)})")
+            kind = kinds[kind]
+        return self._surface_read("cfd_surface_stats_get", int(kind))
+
     # -- monitor history: probes and the flow diagnostics recorded on the device ----
     def enable_monitor(self, capacity, probe_cells=(), diagnostics=True) -> None:
         """cfd_monitor_enable: a ring of ``capacity`` samples (1..2^20) of the
@@ -1277,6 +1359,11 @@ class GpuGroup:
         raise RuntimeError("render failed: rendering runs on one GPU only: a group's ranks each hold a part of the fields")
 
     render_owner = render
+
+    # surfaces: one GPU only (the name has no forwarded prefix: say so here instead of an AttributeError)
+    def select_surface(self, *a, **k):
+        raise RuntimeError("select_surface failed: surface distributions run on one GPU only: a group's ranks each hold "
+                           "a part of the fields")
 
     def step_info(self): return self.ranks[0].step_info()
     def amg_levels(self): return self.ranks[0].amg_levels()

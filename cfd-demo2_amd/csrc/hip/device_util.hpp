@@ -24,6 +24,31 @@ __device__ __forceinline__ float safe_inverse(float v) {
   return fabsf(v) > 1e-14f ? 1.0f / v : 0.0f;
 }
 
+// A fixed-value wall slot's coefficient of a passive scalar: the diffusive part
+// alone (a wall carries no flux), dist_e the distance the momentum wall
+// diffusion uses.  Shared by the scalar assembly, its wall-flux sum (scalar.hip)
+// and the per-face surface channels (surface.hip).
+__device__ __forceinline__ float scalar_wall_coef(float rd, float area, float dist_e) { return rd * area / dist_e; }
+
+// The weighted incremental (West / Welford) update of one quantity, f64, one
+// rounding per operation (include/cfd2_amd.h "Arithmetic of the time
+// statistics"): w the sample's weight, r = w / (W + w) from the host.
+// mean_update: d against the old mean, e against the new one; m2_update: one M
+// plane's term of the pair (q of its first quantity, e of its second).
+// Shared by the per-cell time statistics (timestats.hip) and the per-face
+// surface statistics (surface.hip).
+struct Dev {
+  double d, e;
+};
+__device__ __forceinline__ Dev mean_update(double x, double r, double& m) {
+  Dev q;
+  q.d = x - m;
+  m = m + r * q.d;
+  q.e = x - m;
+  return q;
+}
+__device__ __forceinline__ void m2_update(double w, const Dev& q, double e, double& M) { M += (w * q.d) * e; }
+
 // Loads of a kernel's once-read streams (matrix slots, row headers, the rows'
 // own operands) with the nontemporal policy (NT: global_load ... nt) or the
 // default one.  NT is chosen per launch for the kernels that are the LAST

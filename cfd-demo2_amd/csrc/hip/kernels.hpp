@@ -929,4 +929,49 @@ struct MonitorRecordArgs {
 };
 void launch_monitor_record(const MonitorRecordArgs& a, hipStream_t s);
 
+// ---- surface.hip ----
+// Wall surface distributions (include/cfd2_amd.h "Arithmetic of the surface
+// channels" is the contract): one thread per face of the compact table (cell,
+// slot), all f64 from the f32 inputs, nothing fused.  Channels, each [n] at
+// stride ld (n rounded up to 64): 0 p; 1, 2 the pressure force terms of
+// k_flow_diag; 3, 4 its viscous terms (BCV form: relative to the wall's own
+// velocity); then per field f its wall-flux term (k_scalar_wall_flux's t[0]
+// term, +0 on a slot outside the field's wall selection) and phi_f of the cell.
+// The plain form reads neither BcvArgs::sel nor the table.
+constexpr uint32_t kSurfaceBaseChannels = 5;
+inline uint32_t surface_channels(uint32_t nf) { return kSurfaceBaseChannels + 2u * nf; }
+struct SurfaceField {
+  const float* phi;     // [N]
+  const uint32_t* sel;  // [N] the field's image word (ScalarBC), null: no wall selection
+  float rd;             // density * D
+  int32_t kind;         // 1 fixed value, 2 fixed flux (with sel)
+  float value;
+};
+struct SurfaceArgs {
+  uint32_t n;             // faces
+  uint32_t N;             // cells: the slot arrays' row stride
+  uint32_t nf;            // fields, 0..kTimeStatsMaxFields
+  const uint32_t* cell;   // [n], every entry < N
+  const uint32_t* slot;   // [n], every entry < wf
+  cfd_constants c;
+  const float2* u;
+  const float* p;
+  const float* area;      // fs.area, [k*N + i]
+  const float* nx;
+  const float* ny;
+  const float* dist_e;
+  uint32_t wf;            // the row width of BcvArgs::tab
+  SurfaceField f[kTimeStatsMaxFields];
+  size_t ld;
+  double* out;            // sample: [channels * ld]
+  double* mean;           // accumulate: [channels * ld] each
+  double* m2;
+  double w, r;            // accumulate: the sample's weight and w / (W + w), from the host
+};
+// v null: the plain form
+void launch_surface_sample(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s);
+// the same evaluation, every channel into its mean and M2 (mean_update /
+// m2_update of device_util.hpp) instead of a.out: one launch per sample
+void launch_surface_accumulate(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s);
+
 }  // namespace cfd2

@@ -44,9 +44,8 @@ __device__ __forceinline__ float scalar_coef(float rd, float F, float area, floa
   const float cin = F < 0.0f ? -F : 0.0f;
   return cin + diff;
 }
-// A fixed-value wall slot's coefficient: the diffusive part alone (a wall
-// carries no flux), dist_e the distance the momentum wall diffusion uses
-__device__ __forceinline__ float scalar_wall_coef(float rd, float area, float dist_e) { return rd * area / dist_e; }
+// scalar_wall_coef, a fixed-value wall slot's coefficient: device_util.hpp
+// (surface.hip evaluates the same term per face)
 // Boundary slot k of type bt is a selected wall slot of the cell's image word
 // (kernels.hpp ScalarBC: bits 0..30; the host refuses a selected face beyond)
 __device__ __forceinline__ bool wall_slot(uint32_t sel, uint32_t k, uint32_t bt) {

@@ -27,17 +27,7 @@ namespace cfd2 {
 
 namespace {
 
-// the update of one quantity's mean: d against the old mean, e against the new one
-struct Dev {
-  double d, e;
-};
-__device__ __forceinline__ Dev mean_update(double x, double r, double& m) {
-  Dev q;
-  q.d = x - m;
-  m = m + r * q.d;
-  q.e = x - m;
-  return q;
-}
+// Dev / mean_update / m2_update, the update of one quantity: device_util.hpp
 
 // V = double2 (two cells) or double (one): every plane access of a lane
 template <class V>
@@ -87,7 +77,7 @@ __device__ __forceinline__ void tstats_cells(const TimeStatsArgs& a, uint32_t i,
       Acc<V>::at(uu, k) += wdu[k] * du[k].e;
       Acc<V>::at(uv, k) += wdu[k] * dv[k].e;
       Acc<V>::at(vv, k) += wdv[k] * dv[k].e;
-      Acc<V>::at(pp, k) += (w * dp[k].d) * dp[k].e;
+      m2_update(w, dp[k], dp[k].e, Acc<V>::at(pp, k));
     }
     *plane(3) = uu;
     *plane(4) = uv;
@@ -112,7 +102,7 @@ __device__ __forceinline__ void tstats_cells(const TimeStatsArgs& a, uint32_t i,
 #pragma unroll
       for (int k = 0; k < n; ++k) {
         df[k] = mean_update((double)xf[k], r, Acc<V>::at(mf, k));
-        Acc<V>::at(ff, k) += (w * df[k].d) * df[k].e;
+        m2_update(w, df[k], df[k].e, Acc<V>::at(ff, k));
       }
       *plane(q) = mf;
       *plane(q + 1) = ff;

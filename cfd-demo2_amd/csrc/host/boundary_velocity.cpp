@@ -44,6 +44,7 @@ uint32_t Solver::set_boundary_velocity(uint32_t n, const uint32_t* faces, const 
   }
   CFD_HIP(hipSetDevice(device));
   sync();  // no kernel reads the old image any more
+  ++surface_gen;  // a surface re-derives its channels and resets its statistics (surface.cpp)
   if (n == 0) {
     bcv_sel.clear();
     bcv_max_normal = 0.0;

@@ -843,6 +843,47 @@ cfd_status cfd_monitor_get(cfd_solver* s, uint64_t first, uint64_t count, float*
   return guard([&] { s->s->monitor_get(first, count, time, dt, probes, diag); });
 }
 
+// ------------------------------------------------- wall surface distributions
+cfd_status cfd_surface_select(cfd_solver* s, double x0, double y0, double x1, double y1, int32_t* n_faces) {
+  CHECK_S(s);
+  return guard([&] {
+    const uint32_t n = s->s->surface_select(x0, y0, x1, y1);
+    if (n_faces) *n_faces = (int32_t)n;
+  });
+}
+cfd_status cfd_surface_geometry_get(cfd_solver* s, uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx,
+                                    double* ny, double* area, double* dist_e) {
+  CHECK_S(s);
+  return guard([&] { s->s->surface_geometry(cell, slot, cx, cy, nx, ny, area, dist_e); });
+}
+cfd_status cfd_surface_info_get(cfd_solver* s, cfd_surface_info* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->surface_info(out); });
+}
+cfd_status cfd_surface_sample(cfd_solver* s, double* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->surface_sample(out); });
+}
+cfd_status cfd_surface_stats_enable(cfd_solver* s, int32_t on) {
+  CHECK_S(s);
+  return guard([&] { s->s->surface_stats_enable(on != 0); });
+}
+cfd_status cfd_surface_stats_reset(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] { s->s->surface_stats_reset(); });
+}
+cfd_status cfd_surface_stats_accumulate(cfd_solver* s, double weight) {
+  CHECK_S(s);
+  return guard([&] { s->s->surface_stats_accumulate(weight); });
+}
+cfd_status cfd_surface_stats_get(cfd_solver* s, int32_t kind, double* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->surface_stats_get(kind, out); });
+}
+
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {
   return guard([&] {
     cfd2::Watchdog wd(0, -1, timeout_s, nullptr, nullptr);

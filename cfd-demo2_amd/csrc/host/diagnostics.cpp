@@ -128,19 +128,28 @@ void Solver::get_derived(int kind, double* out) {
   for (uint32_t i = 0; i < N; ++i) out[i] = f[i];
 }
 
+std::vector<uint32_t> Solver::wall_faces_in_box(double x0, double y0, double x1, double y1) const {
+  std::vector<uint32_t> sel;
+  if (x1 < x0) return sel;
+  for (size_t j = 0; j < wall_faces.size(); ++j) {
+    const WallFace& wfc = wall_faces[j];
+    if (wfc.cx >= x0 && wfc.cx <= x1 && wfc.cy >= y0 && wfc.cy <= y1) sel.push_back((uint32_t)j);
+  }
+  return sel;
+}
+
 uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
   CFD_HIP(hipSetDevice(device));
   std::vector<uint16_t> mask;
   uint32_t count = 0;
-  if (!(x1 < x0))
-    for (const WallFace& wfc : wall_faces) {
-      if (!(wfc.cx >= x0 && wfc.cx <= x1 && wfc.cy >= y0 && wfc.cy <= y1)) continue;
-      ++count;
-      if (wfc.cell < topo.c0 || wfc.cell >= topo.c1) continue;
-      if (wfc.slot >= 16) throw std::invalid_argument("force region: wall face beyond slot 15 of its cell");
-      if (mask.empty()) mask.assign(N, 0);
-      mask[wfc.cell - topo.c0] |= (uint16_t)(1u << wfc.slot);
-    }
+  for (const uint32_t j : wall_faces_in_box(x0, y0, x1, y1)) {
+    const WallFace& wfc = wall_faces[j];
+    ++count;
+    if (wfc.cell < topo.c0 || wfc.cell >= topo.c1) continue;
+    if (wfc.slot >= 16) throw std::invalid_argument("force region: wall face beyond slot 15 of its cell");
+    if (mask.empty()) mask.assign(N, 0);
+    mask[wfc.cell - topo.c0] |= (uint16_t)(1u << wfc.slot);
+  }
   region_faces = count;
   ++region_gen;  // wall_motion rebuilds its table of face centres
   region_box[0] = x0, region_box[1] = y0, region_box[2] = x1, region_box[3] = y1;

@@ -27,6 +27,7 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   CFD_HIP(hipSetDevice(device));
   sync();
   sc_arena.release();
+  ++surface_gen;  // a surface re-derives its channels and resets its statistics (surface.cpp)
   sc_count = 0;
   sc_alt = sc_coef = sc_diag = sc_b = nullptr;
   sc_blockmax = nullptr;
@@ -302,6 +303,7 @@ uint32_t Solver::set_scalar_wall(int field, const cfd_scalar_wall& c) {
   ScalarField& f = sc_field[field];
   f.wall = c;
   f.wall_n = count;
+  ++surface_gen;  // a surface re-derives its channels and resets its statistics (surface.cpp)
   scalar_select(f);
   return count;
 }

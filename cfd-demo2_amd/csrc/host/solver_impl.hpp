@@ -612,6 +612,10 @@ struct Solver {
   void flow_diag_device(bool fields, bool reduce);
   static void flow_diag_decode(const uint64_t* sums, const uint64_t* m, uint32_t faces, cfd_flow_diag* out);
   void get_derived(int kind, double* out);
+  // the selection rule of a box of wall faces (the force region and the surface
+  // share it): indices into wall_faces, ascending, of the faces whose f64 centre
+  // lies in the closed box; none for an inverted box (x1 < x0)
+  std::vector<uint32_t> wall_faces_in_box(double x0, double y0, double x1, double y1) const;
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
   // ---- passive scalars (scalar.cpp; kernels.hpp "scalar.hip") ----
@@ -820,6 +824,41 @@ struct Solver {
   void monitor_disable();
   void monitor_record();
   void monitor_get(uint64_t first, uint64_t count, float* time, float* dt, float* probes, cfd_flow_diag* diag);
+  // ---- wall surface distributions (surface.cpp; kernels.hpp "surface.hip") ----
+  // Opt-in and read-only like the time statistics: nothing below is allocated
+  // before surface_select, and step() launches none of it.  One GPU only.
+  // sf_arena holds the face table, sf_ch_arena the channel buffers (sample, mean,
+  // M2): the channel count follows the scalar fields, so those buffers are
+  // re-derived (and the statistics reset) by the first surface call after
+  // surface_gen moved -- scalars_enable, set_scalar_wall and
+  // set_boundary_velocity bump it.  The total weight stays on the host.
+  DeviceArena sf_arena, sf_ch_arena;
+  bool sf_on = false;              // a surface exists (it may have no face)
+  std::vector<uint32_t> sf_face;   // indices into wall_faces, ascending (cell, then slot)
+  uint32_t* sf_cell = nullptr;     // [n]
+  uint32_t* sf_slot = nullptr;     // [n]
+  size_t sf_ld = 0;                // channel stride: n rounded up to 64 (at least 64)
+  uint32_t sf_nch = 0;             // channels the buffers hold
+  double* sf_out = nullptr;        // [sf_nch * sf_ld]
+  double* sf_mean = nullptr;       // with statistics: [sf_nch * sf_ld] each
+  double* sf_m2 = nullptr;
+  bool sf_stats = false;
+  double sf_W = 0.0;               // total weight
+  uint64_t sf_samples = 0;
+  uint64_t surface_gen = 0, sf_gen = 0;  // configuration changes; the one the channel buffers were derived for
+  void surface_need(const char* what);   // throws: distributed, no surface; re-derives the channels
+  void surface_derive();                 // the channel buffers for the current scalar count; statistics reset
+  void surface_clear();
+  SurfaceArgs surface_args();
+  uint32_t surface_select(double x0, double y0, double x1, double y1);
+  void surface_geometry(uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx, double* ny, double* area,
+                        double* dist_e);
+  void surface_info(cfd_surface_info* out);
+  void surface_sample(double* out);
+  void surface_stats_enable(bool on);
+  void surface_stats_reset();
+  void surface_stats_accumulate(double weight);
+  void surface_stats_get(int kind, double* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

@@ -1377,6 +1377,104 @@ cfd_status cfd_monitor_info(cfd_solver* s, uint32_t* capacity, uint32_t* num_pro
 cfd_status cfd_monitor_get(cfd_solver* s, uint64_t first, uint64_t count, float* time, float* dt, float* probes,
                            cfd_flow_diag* diag /* [count] */);
 
+/* ------------------------------------------------------------------------ */
+/* Wall surface distributions: what cfd_flow_diagnostics, cfd_scalar_wall_flux_get
+ * and cfd_wall_motion_get integrate, face by face -- the pressure round a body,
+ * the wall shear (its sign change is the separation point), the local heat flux
+ * of a heated wall, and their time mean and variance -- evaluated on the device
+ * from the current state, so a long run reads back O(sqrt N) f64 values per
+ * sample instead of the fields.  Opt-in, read-only, one GPU only and outside
+ * the checkpoint, as the time statistics above: a handle that never calls
+ * cfd_surface_select allocates and launches nothing new, cfd_step launches none
+ * of it in any case, and nothing a step reads is written.  Handles of
+ * cfd_solver_create_dist* and members of a group of more than one rank return
+ * CFD_ERR_INVALID.
+ *
+ * A surface is the ordered list of the wall faces whose f64 face centre lies in
+ * a closed box: cfd_set_force_region's own rule (one host function serves
+ * both), ordered by ascending cell index, then ascending slot in the cell's
+ * face list.  It is independent of the force region.
+ *
+ * Arithmetic of the surface channels.  Everything f64 from the f32 inputs, one
+ * rounding per operation, left to right as written, nothing fused.  Face j is
+ * slot k of cell i; e = k N + i indexes the face-slot arrays; ad =
+ * (double)area[e]; dist = (double)dist_e[e] (the distance the wall diffusion of
+ * the momentum equation uses).
+ *   0        (double)p[i]
+ *   1, 2     (double)p[i] * (double)nx[e] * ad;  (double)p[i] * (double)ny[e] * ad
+ *   3, 4     (double)viscosity * rux * ad / dist;  (double)viscosity * ruy * ad / dist
+ *            rux = (double)u[i].x, ruy = (double)u[i].y; on a slot the
+ *            boundary-velocity selection moves, rux = (double)u[i].x -
+ *            (double)ubx and likewise ruy, with ubx = bx * (wall_scale * ramp),
+ *            uby = by * (wall_scale * ramp) in f32 ("Arithmetic of boundary
+ *            velocities")
+ *   5 + 2f   field f's wall-flux term: on a slot of the field's wall selection
+ *            (cfd_set_scalar_wall, kind 1 or 2), kind 1: (double)c_k *
+ *            ((double)value - (double)phi_f[i]) with c_k = (density * D) *
+ *            area[e] / dist_e[e] in f32; kind 2: (double)value * ad; +0 on
+ *            every other slot
+ *   6 + 2f   (double)phi_f[i]
+ * 5 + 2 * (enabled scalar fields) channels.  Channels 1-4 are the force of the
+ * fluid on the wall as the assembly discretises it: they are the terms of
+ * cfd_flow_diagnostics' force sums, and channel 5 + 2f the terms of
+ * cfd_scalar_wall_flux_get's flux.  Adding a cell's terms in slot order from +0
+ * and the cells' sums in the canonical order of those calls gives their bits.
+ *
+ * Statistics: per face and channel x, the weighted incremental (West / Welford)
+ * update of "Arithmetic of the time statistics" with the covariance of x with
+ * itself:  host, once per call: w = weight; Wn = W + w; r = w / Wn; then W = Wn;
+ * device:  d = x - m;  m = m + r * d;  e = x - m;  M2 += (w * d) * e.
+ * The evaluation and the update are one kernel launch; the total weight W is
+ * kept on the host (the device divides nothing).
+ *
+ * Configuration changes after cfd_surface_select.  cfd_scalars_enable (any
+ * count), cfd_set_scalar_wall and cfd_set_boundary_velocity are accepted; the
+ * next cfd_surface_* call re-derives the channel count from the scalar fields
+ * enabled then and RESETS the statistics (W = 0, samples = 0, mean and M2
+ * zeroed; they stay enabled), because a mean over two channel sets, wall
+ * selections or wall conditions means nothing.  The surface's faces stay.
+ * Parameter values (viscosity, density, diffusivity, the boundary-velocity
+ * scales, the ramp) are read at each call and reset nothing.                  */
+typedef struct cfd_surface_info {
+  uint32_t faces;
+  uint32_t channels;     /* 5 + 2 * the scalar fields enabled now                  */
+  uint64_t samples;      /* accumulated since the last reset                       */
+  double total_weight;   /* W                                                      */
+  int32_t stats_on;
+  int32_t reserved;
+} cfd_surface_info;
+/* Builds and uploads the face table (cell u32, slot u32) and allocates the
+ * channel buffers, in device memory of the module's own.  A second call
+ * replaces the surface and resets the statistics (they stay enabled).  x1 < x0
+ * clears the surface and frees everything; a box without a wall face gives a
+ * surface of 0 faces.  n_faces may be null.                                   */
+cfd_status cfd_surface_select(cfd_solver* s, double x0, double y0, double x1, double y1, int32_t* n_faces);
+/* Per face, any output null or [faces]: its cell and slot, the f64 face centre
+ * the selection tested, and the f32 normal (out of the cell, into the wall),
+ * area and dist_e the channels are computed from, widened.                    */
+cfd_status cfd_surface_geometry_get(cfd_solver* s, uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx,
+                                    double* ny, double* area, double* dist_e);
+/* Like every cfd_surface_* call it is "the next call" of "Configuration changes"
+ * above: after such a change this query itself re-derives the channels and
+ * resets the statistics, and reports the counts that hold from then on.       */
+cfd_status cfd_surface_info_get(cfd_solver* s, cfd_surface_info* out);
+/* The channels of the current state: one launch, one copy, out[c * faces + j].
+ * CFD_ERR_INVALID: no surface.                                                */
+cfd_status cfd_surface_sample(cfd_solver* s, double* out /* [channels * faces] */);
+/* on != 0 allocates and zeroes mean and M2; 0 frees them.  No change: no-op.  */
+cfd_status cfd_surface_stats_enable(cfd_solver* s, int32_t on);
+/* W = 0, samples = 0, mean and M2 zeroed                                      */
+cfd_status cfd_surface_stats_reset(cfd_solver* s);
+/* One sample of the current state with this weight; weight <= 0: the dt of the
+ * last cfd_step (CFD_ERR_INVALID before any).  Asynchronous like cfd_step: one
+ * launch, no copy, no synchronisation.  CFD_ERR_INVALID, and nothing changes: a
+ * NaN or infinite weight, statistics not enabled.                             */
+cfd_status cfd_surface_stats_accumulate(cfd_solver* s, double weight);
+/* kind 0: the means; 1: the variances M2 / W, divided on the host in f64 after
+ * the read-back (W == 0: the zeros M2 holds).  out[c * faces + j].
+ * CFD_ERR_INVALID: statistics not enabled, another kind.                      */
+cfd_status cfd_surface_stats_get(cfd_solver* s, int32_t kind, double* out /* [channels * faces] */);
+
 #ifdef __cplusplus
 }
 #endif
