@@ -698,12 +698,12 @@ cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_mot
 cfd_status cfd_render_set_polygons(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
                                    const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices) {
   CHECK_S(s);
-  return guard([&] { s->s->render_set_polygons(num_vertices, vx, vy, cell_vertex_offsets, cell_vertices); });
+  return guard([&] { s->s->renderer.set_polygons(s->s->view(cfd2::Renderer::kOneGpu), num_vertices, vx, vy, cell_vertex_offsets, cell_vertices); });
 }
 cfd_status cfd_render_set_view(cfd_solver* s, int32_t width, int32_t height, const double box[4], uint32_t* covered) {
   CHECK_S(s);
   return guard([&] {
-    const uint32_t n = s->s->render_set_view(width, height, box);
+    const uint32_t n = s->s->renderer.set_view(s->s->view(cfd2::Renderer::kOneGpu), width, height, box);
     if (covered) *covered = n;
   });
 }
@@ -716,7 +716,7 @@ cfd_status cfd_render(cfd_solver* s, int32_t field, int32_t scalar_index, const 
 cfd_status cfd_render_owner_get(cfd_solver* s, uint32_t* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->render_owner(out); });
+  return guard([&] { s->s->renderer.owner(s->s->view(cfd2::Renderer::kOneGpu), out); });
 }
 
 // ------------------------------------------------------------ tracer particles
@@ -724,8 +724,10 @@ cfd_status cfd_particles_set_mesh(cfd_solver* s, uint32_t num_vertices, const do
                                   const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices,
                                   const uint32_t* face_v1, const uint32_t* face_v2) {
   CHECK_S(s);
-  return guard(
-      [&] { s->s->particles_set_mesh(num_vertices, vx, vy, cell_vertex_offsets, cell_vertices, face_v1, face_v2); });
+  return guard([&] {
+    s->s->tracers.set_mesh(s->s->view(cfd2::Tracers::kOneGpu), s->s->topo, num_vertices, vx, vy, cell_vertex_offsets, cell_vertices,
+                           face_v1, face_v2);
+  });
 }
 void cfd_particle_config_default(cfd_particle_config* out) {
   if (!out) return;
@@ -734,76 +736,71 @@ void cfd_particle_config_default(cfd_particle_config* out) {
 }
 cfd_status cfd_particles_enable(cfd_solver* s, uint32_t capacity, const cfd_particle_config* cfg) {
   CHECK_S(s);
-  return guard([&] { s->s->particles_enable(capacity, cfg); });
+  return guard([&] { s->s->tracers.enable(s->s->view(cfd2::Tracers::kOneGpu), capacity, cfg); });
 }
 cfd_status cfd_particles_seed(cfd_solver* s, uint32_t first, uint32_t count, const double* x, const double* y) {
   CHECK_S(s);
-  return guard([&] { s->s->particles_seed(first, count, x, y); });
+  return guard([&] { s->s->tracers.seed(s->s->view(cfd2::Tracers::kOneGpu), first, count, x, y); });
 }
 cfd_status cfd_particles_advance(cfd_solver* s, float dt) {
   CHECK_S(s);
-  return guard([&] { s->s->particles_advance(dt); });
+  return guard([&] { s->s->tracers.advance(s->s->view(cfd2::Tracers::kOneGpu), dt); });
 }
 cfd_status cfd_particles_get(cfd_solver* s, uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell,
                              uint32_t* status, float* age) {
   CHECK_S(s);
-  return guard([&] { s->s->particles_get(first, count, x, y, cell, status, age); });
+  return guard([&] { s->s->tracers.get(s->s->view(cfd2::Tracers::kOneGpu), first, count, x, y, cell, status, age); });
 }
 cfd_status cfd_particles_stats_get(cfd_solver* s, cfd_particle_stats* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->particles_stats(out); });
+  return guard([&] { s->s->tracers.stats(s->s->view(cfd2::Tracers::kOneGpu), out); });
 }
 cfd_status cfd_render_particles(cfd_solver* s, uint32_t rgba_colour, uint8_t* rgba) {
   CHECK_S(s);
   if (!rgba) return set_error(CFD_ERR_INVALID, "null rgba");
-  return guard([&] { s->s->render_particles(rgba_colour, rgba); });
+  return guard([&] { s->s->tracers.render_particles(s->s->view(cfd2::Tracers::kOneGpu), s->s->renderer, rgba_colour, rgba); });
 }
 
 // ------------------------------------------- time statistics, monitor history
 cfd_status cfd_tstats_enable(cfd_solver* s, const cfd_tstats_config* cfg) {
   CHECK_S(s);
-  return guard([&] { s->s->tstats_enable(cfg); });
+  return guard([&] { s->s->tstats.enable(s->s->view(cfd2::TimeStats::kOneGpu), cfg); });
 }
 cfd_status cfd_tstats_disable(cfd_solver* s) {
   CHECK_S(s);
-  return guard([&] { s->s->tstats_disable(); });
+  return guard([&] { s->s->tstats.disable(s->s->view(cfd2::TimeStats::kOneGpu)); });
 }
 cfd_status cfd_tstats_reset(cfd_solver* s) {
   CHECK_S(s);
-  return guard([&] { s->s->tstats_reset(); });
+  return guard([&] { s->s->tstats.reset(s->s->view(cfd2::TimeStats::kOneGpu)); });
 }
 cfd_status cfd_tstats_accumulate(cfd_solver* s, float weight) {
   CHECK_S(s);
-  return guard([&] { s->s->tstats_accumulate(weight); });
+  return guard([&] { s->s->tstats.accumulate(s->s->view(cfd2::TimeStats::kOneGpu), weight); });
 }
 cfd_status cfd_tstats_info(cfd_solver* s, uint64_t* samples, double* total_weight, uint32_t* planes) {
   CHECK_S(s);
-  return guard([&] {
-    s->s->tstats_need("cfd_tstats_info");
-    if (samples) *samples = s->s->ts_samples;
-    if (total_weight) *total_weight = s->s->ts_W;
-    if (planes) *planes = s->s->ts_np;
-  });
+  return guard([&] { s->s->tstats.info(s->s->view(cfd2::TimeStats::kOneGpu), samples, total_weight, planes); });
 }
 cfd_status cfd_tstats_get(cfd_solver* s, int32_t kind, int32_t scalar_index, double* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->tstats_get(kind, scalar_index, out); });
+  return guard([&] { s->s->tstats.get(s->s->view(cfd2::TimeStats::kOneGpu), kind, scalar_index, out); });
 }
 cfd_status cfd_tstats_raw_get(cfd_solver* s, uint32_t plane, double* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->tstats_raw(plane, out, nullptr); });
+  return guard([&] { s->s->tstats.raw(s->s->view(cfd2::TimeStats::kOneGpu), plane, out, nullptr); });
 }
 cfd_status cfd_tstats_raw_set(cfd_solver* s, uint32_t plane, const double* in) {
   CHECK_S(s);
   if (!in) return set_error(CFD_ERR_INVALID, "null in");
-  return guard([&] { s->s->tstats_raw(plane, nullptr, in); });
+  return guard([&] { s->s->tstats.raw(s->s->view(cfd2::TimeStats::kOneGpu), plane, nullptr, in); });
 }
 cfd_status cfd_tstats_raw_set_totals(cfd_solver* s, uint64_t samples, double total_weight) {
   CHECK_S(s);
-  return guard([&] { s->s->tstats_set_totals(samples, total_weight); });
+  return guard([&] { s->s->tstats.set_totals(s->s->view(cfd2::TimeStats::kOneGpu), samples, total_weight); });
 }
 cfd_status cfd_monitor_enable(cfd_solver* s, uint32_t capacity, uint32_t num_probes, const uint32_t* probe_cells,
                               int32_t with_diag) {
@@ -812,7 +809,7 @@ cfd_status cfd_monitor_enable(cfd_solver* s, uint32_t capacity, uint32_t num_pro
 }
 cfd_status cfd_monitor_disable(cfd_solver* s) {
   CHECK_S(s);
-  return guard([&] { s->s->monitor_disable(); });
+  return guard([&] { s->s->monitor.disable(s->s->view(cfd2::Monitor::kOneGpu)); });
 }
 cfd_status cfd_monitor_record(cfd_solver* s) {
   CHECK_S(s);
@@ -820,68 +817,61 @@ cfd_status cfd_monitor_record(cfd_solver* s) {
 }
 cfd_status cfd_monitor_count(cfd_solver* s, uint64_t* total, uint64_t* held) {
   CHECK_S(s);
-  return guard([&] {
-    s->s->monitor_need("cfd_monitor_count");
-    if (total) *total = s->s->mon_total;
-    if (held) *held = std::min<uint64_t>(s->s->mon_total, s->s->mon_cap);
-  });
+  return guard([&] { s->s->monitor.count(s->s->view(cfd2::Monitor::kOneGpu), total, held); });
 }
 cfd_status cfd_monitor_info(cfd_solver* s, uint32_t* capacity, uint32_t* num_probes, uint32_t* scalar_fields,
                             int32_t* with_diag) {
   CHECK_S(s);
-  return guard([&] {
-    s->s->monitor_need("cfd_monitor_info");
-    if (capacity) *capacity = s->s->mon_cap;
-    if (num_probes) *num_probes = s->s->mon_P;
-    if (scalar_fields) *scalar_fields = s->s->mon_ns;
-    if (with_diag) *with_diag = s->s->mon_diag ? 1 : 0;
-  });
+  return guard([&] { s->s->monitor.info(s->s->view(cfd2::Monitor::kOneGpu), capacity, num_probes, scalar_fields, with_diag); });
 }
 cfd_status cfd_monitor_get(cfd_solver* s, uint64_t first, uint64_t count, float* time, float* dt, float* probes,
                            cfd_flow_diag* diag) {
   CHECK_S(s);
-  return guard([&] { s->s->monitor_get(first, count, time, dt, probes, diag); });
+  return guard([&] { s->s->monitor.get(s->s->view(cfd2::Monitor::kOneGpu), first, count, time, dt, probes, diag); });
 }
 
 // ------------------------------------------------- wall surface distributions
 cfd_status cfd_surface_select(cfd_solver* s, double x0, double y0, double x1, double y1, int32_t* n_faces) {
   CHECK_S(s);
   return guard([&] {
-    const uint32_t n = s->s->surface_select(x0, y0, x1, y1);
+    const uint32_t n = s->s->surface.select(s->s->view(cfd2::SurfaceDist::kOneGpu), s->s->wall_faces, x0, y0, x1, y1);
     if (n_faces) *n_faces = (int32_t)n;
   });
 }
 cfd_status cfd_surface_geometry_get(cfd_solver* s, uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx,
                                     double* ny, double* area, double* dist_e) {
   CHECK_S(s);
-  return guard([&] { s->s->surface_geometry(cell, slot, cx, cy, nx, ny, area, dist_e); });
+  return guard([&] {
+    s->s->surface.geometry(s->s->view(cfd2::SurfaceDist::kOneGpu), s->s->wall_faces, s->s->topo, cell, slot, cx, cy, nx, ny,
+                           area, dist_e);
+  });
 }
 cfd_status cfd_surface_info_get(cfd_solver* s, cfd_surface_info* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->surface_info(out); });
+  return guard([&] { s->s->surface.info(s->s->view(cfd2::SurfaceDist::kOneGpu), out); });
 }
 cfd_status cfd_surface_sample(cfd_solver* s, double* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->surface_sample(out); });
+  return guard([&] { s->s->surface.sample(s->s->view(cfd2::SurfaceDist::kOneGpu), out); });
 }
 cfd_status cfd_surface_stats_enable(cfd_solver* s, int32_t on) {
   CHECK_S(s);
-  return guard([&] { s->s->surface_stats_enable(on != 0); });
+  return guard([&] { s->s->surface.stats_enable(s->s->view(cfd2::SurfaceDist::kOneGpu), on != 0); });
 }
 cfd_status cfd_surface_stats_reset(cfd_solver* s) {
   CHECK_S(s);
-  return guard([&] { s->s->surface_stats_reset(); });
+  return guard([&] { s->s->surface.stats_reset(s->s->view(cfd2::SurfaceDist::kOneGpu)); });
 }
 cfd_status cfd_surface_stats_accumulate(cfd_solver* s, double weight) {
   CHECK_S(s);
-  return guard([&] { s->s->surface_stats_accumulate(weight); });
+  return guard([&] { s->s->surface.stats_accumulate(s->s->view(cfd2::SurfaceDist::kOneGpu), weight); });
 }
 cfd_status cfd_surface_stats_get(cfd_solver* s, int32_t kind, double* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->surface_stats_get(kind, out); });
+  return guard([&] { s->s->surface.stats_get(s->s->view(cfd2::SurfaceDist::kOneGpu), kind, out); });
 }
 
 cfd_status cfd_debug_comm_watchdog(float timeout_s, int32_t hang_ms) {

@@ -74,7 +74,7 @@ void Solver::flow_diag_device(bool fields, bool reduce) {
   check_launch("flow diagnostics");
 }
 
-void Solver::flow_diag_decode(const uint64_t* sumbits, const uint64_t* m, uint32_t faces, cfd_flow_diag* out) {
+void flow_diag_decode(const uint64_t* sumbits, const uint64_t* m, uint32_t faces, cfd_flow_diag* out) {
   double sums[kFlowDiagSums], smax;
   std::memcpy(sums, sumbits, sizeof(sums));
   std::memcpy(&smax, &m[0], sizeof(double));
@@ -128,11 +128,11 @@ void Solver::get_derived(int kind, double* out) {
   for (uint32_t i = 0; i < N; ++i) out[i] = f[i];
 }
 
-std::vector<uint32_t> Solver::wall_faces_in_box(double x0, double y0, double x1, double y1) const {
+std::vector<uint32_t> wall_faces_in_box(const std::vector<WallFace>& wall, double x0, double y0, double x1, double y1) {
   std::vector<uint32_t> sel;
   if (x1 < x0) return sel;
-  for (size_t j = 0; j < wall_faces.size(); ++j) {
-    const WallFace& wfc = wall_faces[j];
+  for (size_t j = 0; j < wall.size(); ++j) {
+    const WallFace& wfc = wall[j];
     if (wfc.cx >= x0 && wfc.cx <= x1 && wfc.cy >= y0 && wfc.cy <= y1) sel.push_back((uint32_t)j);
   }
   return sel;
@@ -142,7 +142,7 @@ uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
   CFD_HIP(hipSetDevice(device));
   std::vector<uint16_t> mask;
   uint32_t count = 0;
-  for (const uint32_t j : wall_faces_in_box(x0, y0, x1, y1)) {
+  for (const uint32_t j : wall_faces_in_box(wall_faces, x0, y0, x1, y1)) {
     const WallFace& wfc = wall_faces[j];
     ++count;
     if (wfc.cell < topo.c0 || wfc.cell >= topo.c1) continue;
@@ -160,6 +160,33 @@ uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
   CFD_HIP(hipMemcpyAsync(diag_mask, mask.data(), (size_t)N * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
   sync();
   return count;
+}
+
+// ---- the module calls that run the diagnostics first ----
+void Solver::render(int32_t field, int32_t scalar_index, const float* range, uint8_t* rgba, float* used) {
+  const FlowView flow = view(Renderer::kOneGpu);
+  renderer.frame_check(flow, field, scalar_index);
+  const Range rr("render");
+  const float* derived = nullptr;
+  if (field == 4 || field == 5) {
+    flow_diagnostics(nullptr, true);  // the derived pass, its field outputs on
+    derived = field == 4 ? diag_omega : diag_div;
+  }
+  renderer.frame(flow, field, scalar_index, derived, range, rgba, used);
+}
+
+void Solver::monitor_enable(uint32_t capacity, uint32_t num_probes, const uint32_t* cells, bool with_diag) {
+  monitor.enable(view(Monitor::kOneGpu), capacity, num_probes, cells, with_diag);
+  if (with_diag) flow_diag_alloc(false);  // the record itself allocates nothing
+}
+
+void Solver::monitor_record() {
+  const FlowView flow = view(Monitor::kOneGpu);
+  monitor.record_check(flow);
+  const Range range("monitor record");
+  CFD_HIP(hipSetDevice(device));
+  if (monitor.diag) flow_diag_device(false, true);
+  monitor.record(flow, diag_res, region_faces);
 }
 
 float Solver::adapt_dt(double target_cfl) {

@@ -1,51 +1,47 @@
 // Tracer particles (include/cfd2_amd.h "The tracers"; kernels.hpp
 // "particles.hip"): the mesh upload with its per-slot vertex pairs and the bin
 // grid, the particle set, and the calls that seed, advance, count, read and
-// stamp it.  Read-only on the solver's state; every buffer lives in the
-// module's own arenas.
+// stamp it.  Read-only on the solver's state by its type: the solver arrives as
+// a const FlowView, pointers to const, and this file does not see the Solver.
+// Every buffer lives in the module's own arenas.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
 
-#include "solver_impl.hpp"
+#include "modules.hpp"
 
 namespace cfd2 {
 
-namespace {
-const char* kOneGpu = "particles run on one GPU only: a distributed handle holds a part of the fields";
+void Tracers::free_set(const FlowView& flow) {
+  flow.sync();
+  arena.release();
+  frame_arena.release();
+  seed_arena.release();
+  set = ParticleSet{};
+  stats_buf = nullptr;
+  frame = nullptr;
+  frame_pixels = 0;
+  seed_buf = nullptr;
+  seed_cap = 0;
 }
 
-void Solver::particles_free_set() {
-  sync();
-  pt_arena.release();
-  pt_frame_arena.release();
-  pt_seed_arena.release();
-  pt_set = ParticleSet{};
-  pt_stats = nullptr;
-  pt_frame = nullptr;
-  pt_frame_pixels = 0;
-  pt_seed = nullptr;
-  pt_seed_cap = 0;
-}
-
-void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx,
-                                const uint32_t* fv1, const uint32_t* fv2) {
-  if (dist()) throw std::invalid_argument(kOneGpu);
-  CFD_HIP(hipSetDevice(device));
+void Tracers::set_mesh(const FlowView& flow, const Topology& topo, uint32_t nv, const double* vx, const double* vy,
+                       const uint32_t* off, const uint32_t* idx, const uint32_t* fv1, const uint32_t* fv2) {
+  CFD_HIP(hipSetDevice(flow.device));
   if (nv == 0) {
-    particles_free_set();
-    pt_mesh_arena.release();
-    pt_mesh = ParticleMesh{};
+    free_set(flow);
+    mesh_arena.release();
+    mesh = ParticleMesh{};
     return;
   }
   if (!vx || !vy || !off || !idx || !fv1 || !fv2) throw std::invalid_argument("particle mesh: null array");
   if (nv >= kParticleSignBit) throw std::invalid_argument("particle mesh: num_vertices must be below 2^31");
   if (off[0] != 0) throw std::invalid_argument("particle mesh: cell_vertex_offsets[0] must be 0");
-  for (uint32_t c = 0; c < N; ++c)
+  for (uint32_t c = 0; c < flow.N; ++c)
     if (off[c + 1] < off[c])
       throw std::invalid_argument("particle mesh: cell_vertex_offsets decrease at cell " + std::to_string(c));
-  const uint32_t total = off[N];
+  const uint32_t total = off[flow.N];
   if (total >= (1u << 31)) throw std::invalid_argument("particle mesh: cell_vertex_offsets[N] must be below 2^31");
   for (uint32_t k = 0; k < total; ++k)
     if (idx[k] >= nv)
@@ -56,8 +52,8 @@ void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy,
   // every face slot's vertex pair, found as consecutive vertices of the cell's
   // polygon; counter-clockwise polygons (the inner side is on the left)
   const int wf = topo.wf;
-  std::vector<uint32_t> sa((size_t)wf * N, 0u), sb((size_t)wf * N, 0u);
-  for (uint32_t c = 0; c < N; ++c) {
+  std::vector<uint32_t> sa((size_t)wf * flow.N, 0u), sb((size_t)wf * flow.N, 0u);
+  for (uint32_t c = 0; c < flow.N; ++c) {
     const uint32_t* p = idx + off[c];
     const uint32_t n = off[c + 1] - off[c];
     double area2 = 0.0;
@@ -68,7 +64,7 @@ void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy,
     if (!(area2 > 0.0))
       throw std::invalid_argument("particle mesh: the polygon of cell " + std::to_string(c) + " is not counter-clockwise");
     for (uint32_t k = 0; k < topo.nface[c]; ++k) {
-      const size_t e = (size_t)k * N + c;
+      const size_t e = (size_t)k * flow.N + c;
       const uint32_t f = topo.fs_face[e];
       const uint32_t v1 = fv1[f], v2 = fv2[f];
       if (v1 >= nv || v2 >= nv || v1 == v2)
@@ -97,7 +93,7 @@ void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy,
     b[3] = y > b[3] ? y : b[3];
   }
   ParticleMesh m{};
-  m.nb = std::min<uint32_t>(1024u, (uint32_t)std::ceil(std::sqrt((double)N)));
+  m.nb = std::min<uint32_t>(1024u, (uint32_t)std::ceil(std::sqrt((double)flow.N)));
   m.bx0 = b[0];
   m.by0 = b[1];
   m.sx = (b[2] - b[0]) / (float)m.nb;
@@ -105,8 +101,8 @@ void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy,
   if (!(m.sx > 0.0f) || !(m.sy > 0.0f) || !std::isfinite(m.sx) || !std::isfinite(m.sy))
     throw std::invalid_argument("particle mesh: the vertices' bounds are empty or not finite");
   const size_t nbins = (size_t)m.nb * m.nb;
-  std::vector<uint32_t> boff(nbins + 1, 0u), range(4 * (size_t)N);
-  for (uint32_t c = 0; c < N; ++c) {
+  std::vector<uint32_t> boff(nbins + 1, 0u), range(4 * (size_t)flow.N);
+  for (uint32_t c = 0; c < flow.N; ++c) {
     float cb[4] = {inf, inf, -inf, -inf};
     for (uint32_t k = off[c]; k < off[c + 1]; ++k) {
       const float x = fx[idx[k]], y = fy[idx[k]];
@@ -128,154 +124,152 @@ void Solver::particles_set_mesh(uint32_t nv, const double* vx, const double* vy,
     boff[q + 1] += boff[q];
   }
   std::vector<uint32_t> bcells(boff[nbins]), cur(boff.begin(), boff.end() - 1);
-  for (uint32_t c = 0; c < N; ++c) {  // ascending cells: ascending lists
+  for (uint32_t c = 0; c < flow.N; ++c) {  // ascending cells: ascending lists
     const uint32_t* r = &range[4 * (size_t)c];
     for (uint32_t j = r[1]; j <= r[3]; ++j)
       for (uint32_t i = r[0]; i <= r[2]; ++i) bcells[cur[(size_t)j * m.nb + i]++] = c;
   }
   // validated: replace what was there (the particle set refers to the old mesh and goes with it)
-  particles_free_set();
-  pt_mesh_arena.release();
-  pt_mesh = ParticleMesh{};
-  m.vx = pt_mesh_arena.upload(fx, stream);
-  m.vy = pt_mesh_arena.upload(fy, stream);
-  m.off = pt_mesh_arena.upload(std::vector<uint32_t>(off, off + N + 1), stream);
-  m.idx = pt_mesh_arena.upload(std::vector<uint32_t>(idx, idx + total), stream);
-  m.sa = pt_mesh_arena.upload(sa, stream);
-  m.sb = pt_mesh_arena.upload(sb, stream);
-  m.bin_off = pt_mesh_arena.upload(boff, stream);
-  m.bin_cells = pt_mesh_arena.upload(bcells, stream);
-  sync();  // the uploads read host vectors that end here
+  free_set(flow);
+  mesh_arena.release();
+  mesh = ParticleMesh{};
+  m.vx = mesh_arena.upload(fx, flow.stream);
+  m.vy = mesh_arena.upload(fy, flow.stream);
+  m.off = mesh_arena.upload(std::vector<uint32_t>(off, off + flow.N + 1), flow.stream);
+  m.idx = mesh_arena.upload(std::vector<uint32_t>(idx, idx + total), flow.stream);
+  m.sa = mesh_arena.upload(sa, flow.stream);
+  m.sb = mesh_arena.upload(sb, flow.stream);
+  m.bin_off = mesh_arena.upload(boff, flow.stream);
+  m.bin_cells = mesh_arena.upload(bcells, flow.stream);
+  flow.sync();  // the uploads read host vectors that end here
   m.wf = wf;
-  m.N = N;
-  pt_mesh = m;
+  m.N = flow.N;
+  mesh = m;
 }
 
-void Solver::particles_enable(uint32_t capacity, const cfd_particle_config* cfg) {
-  if (dist()) throw std::invalid_argument(kOneGpu);
-  CFD_HIP(hipSetDevice(device));
+void Tracers::enable(const FlowView& flow, uint32_t capacity, const cfd_particle_config* cfg) {
+  CFD_HIP(hipSetDevice(flow.device));
   if (capacity == 0) {
-    particles_free_set();
+    free_set(flow);
     return;
   }
-  if (pt_mesh.N == 0) throw std::invalid_argument("particles: no mesh (cfd_particles_set_mesh)");
+  if (mesh.N == 0) throw std::invalid_argument("particles: no mesh (cfd_particles_set_mesh)");
   if (capacity > (1u << 24)) throw std::invalid_argument("particles: capacity must be 0..2^24");
   int32_t cap = cfg ? cfg->hop_cap : 0;
   if (cap == 0) cap = 64;
   if (cap < 1 || cap > 65536) throw std::invalid_argument("particles: hop_cap must be 1..65536 (0: the default 64)");
-  particles_free_set();
+  free_set(flow);
   ParticleSet p{};
-  p.x = pt_arena.alloc<float>(capacity);
-  p.y = pt_arena.alloc<float>(capacity);
-  p.cell = pt_arena.alloc<uint32_t>(capacity);
-  p.status = pt_arena.alloc<uint32_t>(capacity);
-  p.age = pt_arena.alloc<float>(capacity);
-  p.contacts = pt_arena.alloc<uint32_t>(capacity);
-  p.hops = pt_arena.alloc<uint32_t>(capacity);
-  pt_stats = pt_arena.alloc<unsigned long long>(kParticleStats);
+  p.x = arena.alloc<float>(capacity);
+  p.y = arena.alloc<float>(capacity);
+  p.cell = arena.alloc<uint32_t>(capacity);
+  p.status = arena.alloc<uint32_t>(capacity);
+  p.age = arena.alloc<float>(capacity);
+  p.contacts = arena.alloc<uint32_t>(capacity);
+  p.hops = arena.alloc<uint32_t>(capacity);
+  stats_buf = arena.alloc<unsigned long long>(kParticleStats);
   const size_t bytes = (size_t)capacity * 4;
   for (void* q : {(void*)p.x, (void*)p.y, (void*)p.age, (void*)p.status, (void*)p.contacts, (void*)p.hops})
-    CFD_HIP(hipMemsetAsync(q, 0, bytes, stream));  // EMPTY at (0, 0), age 0
-  CFD_HIP(hipMemsetAsync(p.cell, 0xFF, bytes, stream));
-  sync();
+    CFD_HIP(hipMemsetAsync(q, 0, bytes, flow.stream));  // EMPTY at (0, 0), age 0
+  CFD_HIP(hipMemsetAsync(p.cell, 0xFF, bytes, flow.stream));
+  flow.sync();
   p.n = capacity;
-  pt_set = p;
-  pt_hop_cap = (uint32_t)cap;
+  set = p;
+  hop_cap = (uint32_t)cap;
 }
 
-void Solver::particles_need(const char* what, uint32_t first, uint32_t count) const {
-  if (dist()) throw std::invalid_argument(kOneGpu);
-  if (pt_set.n == 0) throw std::invalid_argument(std::string(what) + ": particles are not enabled (cfd_particles_enable)");
-  if ((uint64_t)first + count > pt_set.n)
-    throw std::invalid_argument(std::string(what) + ": first + count exceeds the capacity " + std::to_string(pt_set.n));
+void Tracers::need(const char* what, uint32_t first, uint32_t count) const {
+  if (set.n == 0) throw std::invalid_argument(std::string(what) + ": particles are not enabled (cfd_particles_enable)");
+  if ((uint64_t)first + count > set.n)
+    throw std::invalid_argument(std::string(what) + ": first + count exceeds the capacity " + std::to_string(set.n));
 }
 
-void Solver::particles_seed(uint32_t first, uint32_t count, const double* x, const double* y) {
-  particles_need("particle seed", first, count);
+void Tracers::seed(const FlowView& flow, uint32_t first, uint32_t count, const double* x, const double* y) {
+  need("particle seed", first, count);
   if (count == 0) return;
   if (!x || !y) throw std::invalid_argument("particle seed: null array");
   const Range range("particle seed");
-  CFD_HIP(hipSetDevice(device));
-  if (count > pt_seed_cap) {  // count <= the capacity <= 2^24
-    sync();
-    pt_seed_arena.release();
-    pt_seed = nullptr;
-    pt_seed_cap = 0;
-    pt_seed = pt_seed_arena.alloc<float>(2 * (size_t)count);
-    pt_seed_cap = count;
+  CFD_HIP(hipSetDevice(flow.device));
+  if (count > seed_cap) {  // count <= the capacity <= 2^24
+    flow.sync();
+    seed_arena.release();
+    seed_buf = nullptr;
+    seed_cap = 0;
+    seed_buf = seed_arena.alloc<float>(2 * (size_t)count);
+    seed_cap = count;
   }
-  pt_seed_host.resize(2 * (size_t)count);
-  for (uint32_t k = 0; k < count; ++k) pt_seed_host[k] = (float)x[k], pt_seed_host[(size_t)count + k] = (float)y[k];
-  CFD_HIP(hipMemcpyAsync(pt_seed, pt_seed_host.data(), 2 * (size_t)count * 4, hipMemcpyHostToDevice, stream));
-  launch_particles_locate(pt_mesh, pt_set, first, count, pt_seed, pt_seed + count, stream);
-  check_launch("particle seed");
-  sync();  // the staging buffers are free for the next call
+  seed_host.resize(2 * (size_t)count);
+  for (uint32_t k = 0; k < count; ++k) seed_host[k] = (float)x[k], seed_host[(size_t)count + k] = (float)y[k];
+  CFD_HIP(hipMemcpyAsync(seed_buf, seed_host.data(), 2 * (size_t)count * 4, hipMemcpyHostToDevice, flow.stream));
+  launch_particles_locate(mesh, set, first, count, seed_buf, seed_buf + count, flow.stream);
+  flow.check_launch("particle seed");
+  flow.sync();  // the staging buffers are free for the next call
 }
 
-void Solver::particles_advance(float dt) {
-  particles_need("particle advance", 0, 0);
+void Tracers::advance(const FlowView& flow, float dt) {
+  need("particle advance", 0, 0);
   if (!(dt > 0.0f)) {
-    if (!(last_step_dt > 0.0f))
+    if (!(flow.last_step_dt > 0.0f))
       throw std::invalid_argument("cfd_particles_advance: dt <= 0 asks for the dt of the last cfd_step, and there was none");
-    dt = last_step_dt;
+    dt = flow.last_step_dt;
   }
   if (!std::isfinite(dt)) throw std::invalid_argument("cfd_particles_advance: dt must be finite");
   const Range range("particle advance");
-  CFD_HIP(hipSetDevice(device));
-  launch_particles_advance(pt_mesh, fs, S().u, pt_set, dt, pt_hop_cap, stream);
-  check_launch("particle advance");
+  CFD_HIP(hipSetDevice(flow.device));
+  launch_particles_advance(mesh, flow.fs, flow.u, set, dt, hop_cap, flow.stream);
+  flow.check_launch("particle advance");
 }
 
-void Solver::particles_get(uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell, uint32_t* status, float* age) {
-  particles_need("particle get", first, count);
+void Tracers::get(const FlowView& flow, uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell,
+                  uint32_t* status, float* age) {
+  need("particle get", first, count);
   if (count == 0) return;
-  CFD_HIP(hipSetDevice(device));
+  CFD_HIP(hipSetDevice(flow.device));
   const size_t bytes = (size_t)count * 4;
-  const std::pair<void*, const void*> io[] = {{x, pt_set.x},           {y, pt_set.y},    {cell, pt_set.cell},
-                                              {status, pt_set.status}, {age, pt_set.age}};
+  const std::pair<void*, const void*> io[] = {{x, set.x},           {y, set.y},    {cell, set.cell},
+                                              {status, set.status}, {age, set.age}};
   for (const auto& q : io)
-    if (q.first) CFD_HIP(hipMemcpyAsync(q.first, (const char*)q.second + (size_t)first * 4, bytes, hipMemcpyDeviceToHost, stream));
-  sync();
+    if (q.first) CFD_HIP(hipMemcpyAsync(q.first, (const char*)q.second + (size_t)first * 4, bytes, hipMemcpyDeviceToHost, flow.stream));
+  flow.sync();
 }
 
-void Solver::particles_stats(cfd_particle_stats* out) {
-  particles_need("particle stats", 0, 0);
-  CFD_HIP(hipSetDevice(device));
-  CFD_HIP(hipMemsetAsync(pt_stats, 0, kParticleStats * sizeof(unsigned long long), stream));
-  launch_particles_stats(pt_set, pt_stats, stream);
-  check_launch("particle stats");
+void Tracers::stats(const FlowView& flow, cfd_particle_stats* out) {
+  need("particle stats", 0, 0);
+  CFD_HIP(hipSetDevice(flow.device));
+  CFD_HIP(hipMemsetAsync(stats_buf, 0, kParticleStats * sizeof(unsigned long long), flow.stream));
+  launch_particles_stats(set, stats_buf, flow.stream);
+  flow.check_launch("particle stats");
   unsigned long long h[kParticleStats] = {};
-  CFD_HIP(hipMemcpyAsync(h, pt_stats, sizeof(h), hipMemcpyDeviceToHost, stream));
-  sync();
+  CFD_HIP(hipMemcpyAsync(h, stats_buf, sizeof(h), hipMemcpyDeviceToHost, flow.stream));
+  flow.sync();
   *out = cfd_particle_stats{};
   for (int k = 0; k < 5; ++k) out->count[k] = h[k];
   out->wall_contacts = h[5];
   out->hops_total = h[6];
   out->hops_max = h[7];
   out->capped = h[8];
-  out->capacity = pt_set.n;
+  out->capacity = set.n;
 }
 
-void Solver::render_particles(uint32_t colour, uint8_t* rgba) {
-  particles_need("render particles", 0, 0);
-  if (rd_view.W == 0) throw std::invalid_argument("render particles: no view (cfd_render_set_view)");
-  if (!rd_rendered) throw std::invalid_argument("render particles: no frame of this view yet (cfd_render)");
+void Tracers::render_particles(const FlowView& flow, const Renderer& r, uint32_t colour, uint8_t* rgba) {
+  need("render particles", 0, 0);
+  const Renderer::Frame rf = r.current_frame("render particles");
   const Range range("render particles");
-  CFD_HIP(hipSetDevice(device));
-  if (pt_frame_pixels != rd_pixels) {
-    sync();
-    pt_frame_arena.release();
-    pt_frame = nullptr;
-    pt_frame_pixels = 0;
-    pt_frame = pt_frame_arena.alloc<uint32_t>(rd_pixels);
-    pt_frame_pixels = rd_pixels;
+  CFD_HIP(hipSetDevice(flow.device));
+  if (frame_pixels != rf.pixels) {
+    flow.sync();
+    frame_arena.release();
+    frame = nullptr;
+    frame_pixels = 0;
+    frame = frame_arena.alloc<uint32_t>(rf.pixels);
+    frame_pixels = rf.pixels;
   }
-  const size_t bytes = rd_pixels * sizeof(uint32_t);
-  CFD_HIP(hipMemcpyAsync(pt_frame, rd_image, bytes, hipMemcpyDeviceToDevice, stream));
-  launch_particles_stamp(pt_set, rd_view, colour, pt_frame, stream);
-  check_launch("render particles");
-  CFD_HIP(hipMemcpyAsync(rgba, pt_frame, bytes, hipMemcpyDeviceToHost, stream));
-  sync();
+  const size_t bytes = rf.pixels * sizeof(uint32_t);
+  CFD_HIP(hipMemcpyAsync(frame, rf.image, bytes, hipMemcpyDeviceToDevice, flow.stream));
+  launch_particles_stamp(set, rf.view, colour, frame, flow.stream);
+  flow.check_launch("render particles");
+  CFD_HIP(hipMemcpyAsync(rgba, frame, bytes, hipMemcpyDeviceToHost, flow.stream));
+  flow.sync();
 }
 
 }  // namespace cfd2

@@ -62,12 +62,7 @@ void Solver::scalars_enable(int count, const cfd_scalar_config& c) {
   sc_count = count;
 }
 
-void Solver::scalar_check(int field) const {
-  if (sc_count == 0) throw std::invalid_argument("passive scalars are not enabled (cfd_scalars_enable)");
-  if (field < 0 || field >= sc_count)
-    throw std::invalid_argument("scalar field index " + std::to_string(field) + " outside [0, " +
-                                std::to_string(sc_count) + ")");
-}
+void Solver::scalar_check(int field) const { scalar_index_check(sc_count, field); }
 
 void Solver::set_scalar(int field, const double* phi) {
   scalar_check(field);

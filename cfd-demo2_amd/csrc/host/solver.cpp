@@ -212,6 +212,24 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
   sync();
 }
 
+FlowView Solver::view(const char* one_gpu_message) const {
+  if (dist()) throw std::invalid_argument(one_gpu_message);
+  auto field = [&](int f) {
+    SurfaceField d{};
+    if (f >= sc_count) return d;
+    const ScalarField& s = sc_field[f];
+    d.phi = s.phi;
+    d.sel = s.wall_on() ? s.sel : nullptr;  // scalar_wall_flux's own condition
+    d.rd = constants.density * s.par.diffusivity;
+    d.kind = s.wall.kind;
+    d.value = s.wall.value;
+    return d;
+  };
+  return FlowView{device,   stream,   N,        NG,       fs,           constants,  ring[i_state].u, ring[i_state].p,
+                  sc_count, {field(0), field(1), field(2), field(3)},   last_step_dt, bcv_args(),    bcv_on(),
+                  surface_gen, check_sync};
+}
+
 Solver::~Solver() {
   if (stream) (void)hipStreamSynchronize(stream);
   for (IterGraph& G : graphs) {

@@ -1,7 +1,6 @@
 // Host-side driver state of the HIP solver (one instance per GPU handle).
 #pragma once
 #include <hip/hip_runtime_api.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
 #include <cstdint>
@@ -16,138 +15,19 @@
 #include "../hip/amg_setup.hpp"
 #include "../hip/kernels.hpp"
 #include "comm.hpp"
+#include "device_mem.hpp"
 #include "dist.hpp"
+#include "modules.hpp"
+#include "topology.hpp"
 #include "tuning.hpp"
 
 namespace cfd2 {
-
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define CFD_HIP(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess)                                                               \
-      throw ::cfd2::HipError(std::string(#expr) + ": " + hipGetErrorString(_e));        \
-  } while (0)
-
-// Device allocation arena: every buffer is freed with the solver.
-class DeviceArena {
- public:
-  ~DeviceArena() { release(); }
-  template <class T>
-  T* alloc(size_t n) {
-    void* p = nullptr;
-    const size_t bytes = (n ? n : 1) * sizeof(T);
-    CFD_HIP(hipMalloc(&p, bytes));
-    ptrs_.push_back(p);
-    bytes_ += bytes;
-    return static_cast<T*>(p);
-  }
-  template <class T>
-  T* upload(const std::vector<T>& v, hipStream_t s, size_t slack = 0) {
-    // slack: zeroed elements after the data (16-byte vector reads that start
-    // at any valid index, e.g. the fused prolongation's agg gathers)
-    T* p = alloc<T>(v.size() + slack);
-    if (slack) CFD_HIP(hipMemsetAsync(p + v.size(), 0, slack * sizeof(T), s));
-    if (!v.empty()) CFD_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return p;
-  }
-  void swap(DeviceArena& o) {
-    ptrs_.swap(o.ptrs_);
-    std::swap(bytes_, o.bytes_);
-  }
-  void release() {
-    for (void* p : ptrs_) (void)hipFree(p);
-    ptrs_.clear();
-    bytes_ = 0;
-  }
-  size_t bytes() const { return bytes_; }
-
- private:
-  std::vector<void*> ptrs_;
-  size_t bytes_ = 0;
-};
-
-// temporary device buffer (setup scratch; the arena holds what the V-cycle keeps)
-template <class T>
-struct DevTmp {
-  T* p = nullptr;
-  explicit DevTmp(size_t n) { CFD_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(T))); }
-  DevTmp(const DevTmp&) = delete;
-  DevTmp& operator=(const DevTmp&) = delete;
-  ~DevTmp() { (void)hipFree(p); }
-};
-
-// roctx range (rocprofv3 --marker-trace shows steps, Picard iterations,
-// FGMRES solves and iterations, AMG setup / refresh, checkpoint I/O)
-struct Range {
-  explicit Range(const char* what) { roctxRangePushA(what); }
-  ~Range() { roctxRangePop(); }
-  Range(const Range&) = delete;
-  Range& operator=(const Range&) = delete;
-};
 
 struct HostCsr {
   std::vector<uint32_t> row, col;
   std::vector<float> val;
   size_t rows = 0, cols = 0;
 };
-
-// Mesh-derived static topology/geometry (init/mesh.rs + the per-slot geometric
-// factors every face sweep needs), computed once on the host in f32 with the
-// exact operation order of the WGSL expressions they replace.
-struct Topology {
-  uint32_t N = 0, F = 0;  // N = owned cells
-  // distributed view (one GPU: c0 = 0, c1 = NG, no ghosts)
-  uint32_t NG = 0, c0 = 0, c1 = 0;
-  uint32_t npad = 0;           // N rounded up to 64: first upper-ghost local index
-  uint32_t glo = 0, ghi = 0;   // ghosts below c0 / at or above c1
-  std::vector<uint32_t> ghost; // ghost global ids, ascending
-  RowWindow window() const { return RowWindow(c0, c1, ghost, glo); }
-  // signed local index of a global cell id (owned or ghost)
-  int32_t rel(uint32_t g) const { return window().rel(g); }
-  int wf = 0;  // max faces per cell
-  int ws = 0;  // max scalar row length (incl. diagonal)
-  std::vector<float> vol;
-  std::vector<uint32_t> nface;
-  // face slots, [k*N + i]
-  std::vector<int32_t> fs_other;
-  std::vector<uint32_t> fs_meta;
-  std::vector<uint32_t> fs_face;  // host only: face index of each slot
-  std::vector<float> fs_area, fs_nx, fs_ny, fs_lam_s, fs_lam_f, fs_dist_a, fs_dist_e, fs_dvx,
-      fs_dvy, fs_rx, fs_ry, fs_rox, fs_roy;
-  // scalar CSR rows of the owned cells (init/mesh.rs:27-53), global columns,
-  // and its ELL image [r*N + i] with signed local columns
-  std::vector<uint32_t> srow, scol;
-  uint32_t ld = 0;               // ELL slot stride (= npad)
-  std::vector<int32_t> ell_col;  // [r*ld + i]
-  std::vector<uint32_t> ell_len, ell_drank;  // [ld]
-  bool use16 = false;            // every |col - row| < 2^15: ell_col16 valid
-  std::vector<int16_t> ell_col16;
-  std::vector<uint8_t> ell_len8, ell_drank8;
-  // Coupled-matrix ELL (CoupledMatrix, kernels.hpp): the same rows with their
-  // entries moved to aligned slots.  tmode[r] = the most frequent column - row
-  // of slot r over the full rows; a row with fewer entries places each entry,
-  // in CSR order, at the first slot still free whose mode is its delta, so
-  // missing neighbours (walls) leave gaps instead of shifting the rest of the
-  // row, and 4 consecutive rows keep 4 consecutive columns per slot.  Gaps and
-  // trailing slots hold the virtual column row + tmode[r] (clamped into the
-  // vectors' range; never accumulated).  Position layout when ws > 8 (the
-  // Voronoi meshes).
-  std::vector<int32_t> tmode;
-  std::vector<uint8_t> tslot;    // [nnz] slot of CSR entry k
-  std::vector<int32_t> tcol;     // [r*ld + i]
-  std::vector<int16_t> tcol16;   // (use16)
-  std::vector<uint16_t> tlg;     // [ld] slots in use | gap mask << 8
-  std::vector<uint8_t> tdrank8;  // [ld] slot of the diagonal
-};
-
-// Throws std::invalid_argument on inconsistent meshes.
-void build_topology(const cfd_mesh_view& m, Topology& t);
-// Owned range [c0, c1) of a distributed rank, ghosts from the face neighbours.
-void build_topology(const cfd_mesh_view& m, Topology& t, uint32_t c0, uint32_t c1);
 
 // AMG hierarchy (linear_solver/amg.rs:84-235, 374-595) built on the host.
 struct AmgHostLevel {
@@ -421,18 +301,7 @@ struct Solver {
   void get_d_p(double* dp);
   void rotate();
   void sync() { CFD_HIP(hipStreamSynchronize(stream)); }
-  // Launch-error check: hipGetLastError after each phase of the step (a host
-  // call, no synchronisation); with cfg.log_level >= 3 the stream is also
-  // synchronised there, so an asynchronous kernel fault is reported at the
-  // phase that caused it (debug runs).
-  void check_launch(const char* where) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw HipError(std::string("kernel launch in ") + where + ": " + hipGetErrorString(e));
-    if (check_sync) {
-      const hipError_t e2 = hipStreamSynchronize(stream);
-      if (e2 != hipSuccess) throw HipError(std::string("kernel execution in ") + where + ": " + hipGetErrorString(e2));
-    }
-  }
+  void check_launch(const char* where) { cfd2::check_launch(stream, check_sync, where); }  // flow_view.hpp
   // image of a global per-cell array (f64 input or f32 checkpoint) in this
   // rank's local layout (owned + ghosts)
   template <class G>
@@ -587,12 +456,7 @@ struct Solver {
   // Read-only on the current state; every device buffer below is allocated on
   // first use.  Collective on a distributed solver (the ghosts of u are current
   // after set_u, step and load_state); R ranks give one GPU's bits.
-  struct WallFace {     // every wall face of the WHOLE mesh, f64 centre
-    double cx, cy;
-    uint32_t cell;      // global owner cell
-    uint32_t slot;      // its slot in the owner's face list
-  };
-  std::vector<WallFace> wall_faces;
+  std::vector<WallFace> wall_faces;  // every wall face of the WHOLE mesh (topology.hpp)
   double min_cell = 0.0;             // min sqrt(cell_vol) over the whole mesh (f64)
   double* diag_partial = nullptr;    // [6 * pstride] unit partials
   unsigned long long* diag_blockmax = nullptr;
@@ -605,17 +469,12 @@ struct Solver {
   bool region_on = false;
   uint32_t region_faces = 0;         // selected wall faces, whole mesh
   void flow_diagnostics(cfd_flow_diag* out, bool fields = false);
-  // its two halves: the launches that leave the sums and maxima in diag_res
-  // (reduce false: the pass alone, for the derived fields), and the decoding of
-  // the words read back (sums: the six f64 patterns, m: the three maximum keys)
+  // its device half: the launches that leave the sums and maxima in diag_res
+  // (reduce false: the pass alone, for the derived fields); flow_diag_decode
+  // (modules.hpp) decodes the words read back
   void flow_diag_alloc(bool fields);
   void flow_diag_device(bool fields, bool reduce);
-  static void flow_diag_decode(const uint64_t* sums, const uint64_t* m, uint32_t faces, cfd_flow_diag* out);
   void get_derived(int kind, double* out);
-  // the selection rule of a box of wall faces (the force region and the surface
-  // share it): indices into wall_faces, ascending, of the faces whose f64 centre
-  // lies in the closed box; none for an inverted box (x1 < x0)
-  std::vector<uint32_t> wall_faces_in_box(double x0, double y0, double x1, double y1) const;
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
   // ---- passive scalars (scalar.cpp; kernels.hpp "scalar.hip") ----
@@ -737,128 +596,23 @@ struct Solver {
   uint64_t region_gen = 0, wm_gen = 0;  // set_force_region calls; the one wm_crow / wm_ctr were built for
   double region_box[4] = {0, 0, -1, 0};
   void wall_motion(double x0, double y0, cfd_wall_motion* out);
-  // ---- frames on the device (render.cpp; kernels.hpp "render.hip") ----
-  // Opt-in and read-only: nothing below is allocated before render_set_polygons,
-  // and step() launches none of it.  One GPU only.  rd_arena holds what depends
-  // on the polygons, rd_view_arena the map and the image of the current view
-  // size; render_set_polygons(0, ...) releases both.
-  DeviceArena rd_arena, rd_view_arena;
-  RenderPolys rd_polys{};          // N = 0: no polygons
-  float rd_bounds[4] = {};         // x0, y0, x1, y1 of the polygons' vertices (f32)
-  uint32_t* rd_list = nullptr;     // [N] the cells that take the wavefront path
-  uint32_t* rd_counts = nullptr;   // [4] listed cells, owned pixels, the auto range's two keys
-  uint32_t* rd_blockmm = nullptr;  // [2 * render_range_blocks(N)]
-  RenderView rd_view{};            // W = 0: no view
-  size_t rd_pixels = 0;            // pixels rd_map / rd_image hold
-  uint32_t* rd_map = nullptr;      // [H * W] owner or kRenderNone
-  uint32_t* rd_image = nullptr;    // [H * W] packed RGBA8
-  uint32_t rd_listed = 0;          // cells of the current view's list
-  bool rd_rendered = false;        // rd_image holds a frame of the current view (render_particles copies it)
-  void render_release();
-  void render_set_polygons(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx);
-  uint32_t render_set_view(int32_t w, int32_t h, const double* box);  // returns the owned pixels
+  // ---- the opt-in post-processing modules (modules.hpp) ----
+  // Each reads the solver through view() alone; nothing of theirs is allocated
+  // before their first enabling call, and step() launches none of it.
+  Renderer renderer;
+  Tracers tracers;
+  TimeStats tstats;
+  Monitor monitor;
+  SurfaceDist surface;
+  uint64_t surface_gen = 0;  // scalars_enable, set_scalar_wall and set_boundary_velocity bump it (FlowView::surface_gen)
+  // The modules' view of this solver, built fresh for every call (the ring
+  // rotates); throws std::invalid_argument(one_gpu_message) on a distributed handle.
+  FlowView view(const char* one_gpu_message) const;
+  // the three module calls that need the flow diagnostics (diagnostics.cpp): a
+  // frame of the vorticity or the divergence, and a monitor with diagnostics
   void render(int32_t field, int32_t scalar_index, const float* range, uint8_t* rgba, float* used);
-  void render_owner(uint32_t* out);
-  // ---- tracer particles (particles.cpp; kernels.hpp "particles.hip") ----
-  // Opt-in and read-only like the renderer: nothing below is allocated before
-  // particles_set_mesh, and step() launches none of it.  One GPU only.
-  // pt_mesh_arena holds the mesh upload, pt_arena the particle set,
-  // pt_frame_arena the stamped copy of a frame, pt_seed_arena the seeds'
-  // staging buffer (grown when a seed call brings more than it holds, so a
-  // rake re-seeded every step allocates once); a new or released mesh frees
-  // the set too (its cells refer to the mesh it was located in).
-  DeviceArena pt_mesh_arena, pt_arena, pt_frame_arena, pt_seed_arena;
-  ParticleMesh pt_mesh{};                 // N = 0: no mesh
-  ParticleSet pt_set{};                   // n = 0: not enabled
-  uint32_t pt_hop_cap = 64;
-  unsigned long long* pt_stats = nullptr; // [kParticleStats]
-  uint32_t* pt_frame = nullptr;           // [pt_frame_pixels] packed RGBA8
-  size_t pt_frame_pixels = 0;
-  float* pt_seed = nullptr;               // [2 * pt_seed_cap]: x, then y
-  uint32_t pt_seed_cap = 0;
-  std::vector<float> pt_seed_host;        // the f32 seeds on their way up
-  void particles_free_set();
-  void particles_need(const char* what, uint32_t first, uint32_t count) const;  // throws: distributed, not enabled, range
-  void particles_set_mesh(uint32_t nv, const double* vx, const double* vy, const uint32_t* off, const uint32_t* idx,
-                          const uint32_t* fv1, const uint32_t* fv2);
-  void particles_enable(uint32_t capacity, const cfd_particle_config* cfg);
-  void particles_seed(uint32_t first, uint32_t count, const double* x, const double* y);
-  void particles_advance(float dt);
-  void particles_get(uint32_t first, uint32_t count, float* x, float* y, uint32_t* cell, uint32_t* status, float* age);
-  void particles_stats(cfd_particle_stats* out);
-  void render_particles(uint32_t colour, uint8_t* rgba);
-  // ---- time statistics and the monitor history (timestats.cpp; kernels.hpp "timestats.hip") ----
-  // Opt-in and read-only like the particles: nothing below is allocated before
-  // tstats_enable / monitor_enable, and step() launches none of it.  One GPU
-  // only.  ts_arena holds the planes, mon_arena the monitor's ring.
-  DeviceArena ts_arena, mon_arena;
-  double* ts_planes = nullptr;     // [ts_np * ts_ld]; null: not enabled
-  uint32_t ts_np = 0;              // planes (tstats_planes)
-  size_t ts_ld = 0;                // plane stride: N rounded up to 32 doubles
-  bool ts_m2 = false;              // second moments
-  bool ts_scalars = false;         // the configuration asked for the scalar fields
-  uint32_t ts_nf = 0;              // fields the planes hold: sc_count at tstats_enable (0 without ts_scalars)
-  double ts_W = 0.0;               // total weight
-  uint64_t ts_samples = 0;
-  void tstats_need(const char* what) const;  // throws: distributed, not enabled
-  void tstats_enable(const cfd_tstats_config* cfg);
-  void tstats_disable();
-  void tstats_reset();
-  void tstats_accumulate(float weight);
-  int tstats_plane_of(int kind, int scalar_index, bool* covariance) const;  // throws: plane off, bad kind / index
-  void tstats_get(int kind, int scalar_index, double* out);
-  void tstats_raw(uint32_t plane, double* out, const double* in);  // one of the two is null
-  void tstats_set_totals(uint64_t samples, double W);
-  // the monitor: a ring of mon_cap slots, sample k in slot k % mon_cap
-  uint32_t mon_cap = 0;            // 0: not enabled
-  uint32_t mon_P = 0, mon_ns = 0;
-  bool mon_diag = false;
-  uint64_t mon_total = 0;          // samples ever recorded
-  uint32_t* mon_cells = nullptr;   // [P]
-  float* mon_time = nullptr;       // [cap][2] time, dt
-  float* mon_probe = nullptr;      // [cap][P][3 + ns]
-  uint64_t* mon_dres = nullptr;    // [cap][kMonitorDiagWords] (with diagnostics)
-  std::vector<uint32_t> mon_faces; // [cap] region_faces at each record (host: the force region is host state)
-  void monitor_need(const char* what) const;
   void monitor_enable(uint32_t capacity, uint32_t num_probes, const uint32_t* cells, bool with_diag);
-  void monitor_disable();
   void monitor_record();
-  void monitor_get(uint64_t first, uint64_t count, float* time, float* dt, float* probes, cfd_flow_diag* diag);
-  // ---- wall surface distributions (surface.cpp; kernels.hpp "surface.hip") ----
-  // Opt-in and read-only like the time statistics: nothing below is allocated
-  // before surface_select, and step() launches none of it.  One GPU only.
-  // sf_arena holds the face table, sf_ch_arena the channel buffers (sample, mean,
-  // M2): the channel count follows the scalar fields, so those buffers are
-  // re-derived (and the statistics reset) by the first surface call after
-  // surface_gen moved -- scalars_enable, set_scalar_wall and
-  // set_boundary_velocity bump it.  The total weight stays on the host.
-  DeviceArena sf_arena, sf_ch_arena;
-  bool sf_on = false;              // a surface exists (it may have no face)
-  std::vector<uint32_t> sf_face;   // indices into wall_faces, ascending (cell, then slot)
-  uint32_t* sf_cell = nullptr;     // [n]
-  uint32_t* sf_slot = nullptr;     // [n]
-  size_t sf_ld = 0;                // channel stride: n rounded up to 64 (at least 64)
-  uint32_t sf_nch = 0;             // channels the buffers hold
-  double* sf_out = nullptr;        // [sf_nch * sf_ld]
-  double* sf_mean = nullptr;       // with statistics: [sf_nch * sf_ld] each
-  double* sf_m2 = nullptr;
-  bool sf_stats = false;
-  double sf_W = 0.0;               // total weight
-  uint64_t sf_samples = 0;
-  uint64_t surface_gen = 0, sf_gen = 0;  // configuration changes; the one the channel buffers were derived for
-  void surface_need(const char* what);   // throws: distributed, no surface; re-derives the channels
-  void surface_derive();                 // the channel buffers for the current scalar count; statistics reset
-  void surface_clear();
-  SurfaceArgs surface_args();
-  uint32_t surface_select(double x0, double y0, double x1, double y1);
-  void surface_geometry(uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx, double* ny, double* area,
-                        double* dist_e);
-  void surface_info(cfd_surface_info* out);
-  void surface_sample(double* out);
-  void surface_stats_enable(bool on);
-  void surface_stats_reset();
-  void surface_stats_accumulate(double weight);
-  void surface_stats_get(int kind, double* out);
   // ---- checkpoint / resume (checkpoint.cpp, cfd_state_file_header) ----
   void save_state(const char* path);  // collective on a distributed solver
   void load_state(const char* path);

@@ -1,98 +1,96 @@
 // Wall surface distributions (include/cfd2_amd.h "Wall surface distributions";
 // kernels.hpp "surface.hip"): the face table of a box of wall faces, the
 // per-face channels of the current state and their running mean and variance.
-// Read-only on the solver's state; every buffer lives in the module's own arenas.
+// Read-only on the solver's state by its type: the solver arrives as a const
+// FlowView, pointers to const, and this file does not see the Solver.  Every
+// buffer lives in the module's own arenas.
 #include <cmath>
 #include <cstring>
 
-#include "solver_impl.hpp"
+#include "modules.hpp"
 
 namespace cfd2 {
 
-namespace {
-const char* kSurfaceOneGpu = "surface distributions run on one GPU only: a distributed handle holds a part of the fields";
-}  // namespace
-
-void Solver::surface_clear() {
-  CFD_HIP(hipSetDevice(device));
-  sync();
-  sf_arena.release();
-  sf_ch_arena.release();
-  sf_on = false;
-  sf_face.clear();
-  sf_cell = sf_slot = nullptr;
-  sf_ld = 0;
-  sf_nch = 0;
-  sf_out = sf_mean = sf_m2 = nullptr;
-  sf_stats = false;
-  sf_W = 0.0;
-  sf_samples = 0;
+void SurfaceDist::clear(const FlowView& flow) {
+  CFD_HIP(hipSetDevice(flow.device));
+  flow.sync();
+  arena.release();
+  ch_arena.release();
+  on = false;
+  face.clear();
+  cell = slot = nullptr;
+  ld = 0;
+  nch = 0;
+  out = mean = m2 = nullptr;
+  stats = false;
+  W = 0.0;
+  samples = 0;
 }
 
 // The channel buffers for the scalar fields enabled now.  The statistics keep
 // their on / off state and start afresh: a mean over samples of two different
 // channel sets, wall selections or wall conditions means nothing.
-void Solver::surface_derive() {
-  CFD_HIP(hipSetDevice(device));
-  sync();
-  sf_ch_arena.release();
-  sf_mean = sf_m2 = nullptr;
-  sf_nch = surface_channels((uint32_t)sc_count);
-  const size_t len = (size_t)sf_nch * sf_ld;
-  sf_out = sf_ch_arena.alloc<double>(len);
-  if (sf_stats) {
-    sf_mean = sf_ch_arena.alloc<double>(len);
-    sf_m2 = sf_ch_arena.alloc<double>(len);
-    CFD_HIP(hipMemsetAsync(sf_mean, 0, len * sizeof(double), stream));
-    CFD_HIP(hipMemsetAsync(sf_m2, 0, len * sizeof(double), stream));
+void SurfaceDist::derive(const FlowView& flow) {
+  CFD_HIP(hipSetDevice(flow.device));
+  flow.sync();
+  ch_arena.release();
+  mean = m2 = nullptr;
+  nch = surface_channels((uint32_t)flow.nf);
+  const size_t len = (size_t)nch * ld;
+  out = ch_arena.alloc<double>(len);
+  if (stats) {
+    mean = ch_arena.alloc<double>(len);
+    m2 = ch_arena.alloc<double>(len);
+    CFD_HIP(hipMemsetAsync(mean, 0, len * sizeof(double), flow.stream));
+    CFD_HIP(hipMemsetAsync(m2, 0, len * sizeof(double), flow.stream));
   }
-  sf_W = 0.0;
-  sf_samples = 0;
-  sf_gen = surface_gen;
+  W = 0.0;
+  samples = 0;
+  gen = flow.surface_gen;
 }
 
-void Solver::surface_need(const char* what) {
-  if (dist()) throw std::invalid_argument(kSurfaceOneGpu);
-  if (!sf_on) throw std::invalid_argument(std::string(what) + ": no surface is selected (cfd_surface_select)");
-  if (sf_gen != surface_gen) surface_derive();
+void SurfaceDist::need(const FlowView& flow, const char* what) {
+  if (!on) throw std::invalid_argument(std::string(what) + ": no surface is selected (cfd_surface_select)");
+  if (gen != flow.surface_gen) derive(flow);
 }
 
-uint32_t Solver::surface_select(double x0, double y0, double x1, double y1) {
-  if (dist()) throw std::invalid_argument(kSurfaceOneGpu);
+uint32_t SurfaceDist::select(const FlowView& flow, const std::vector<WallFace>& wall, double x0, double y0, double x1,
+                             double y1) {
   if (x1 < x0) {
-    surface_clear();
+    clear(flow);
     return 0;
   }
-  std::vector<uint32_t> face = wall_faces_in_box(x0, y0, x1, y1);
-  const uint32_t wf = (uint32_t)topo.wf;
-  std::vector<uint32_t> cell(face.size()), slot(face.size());
-  for (size_t j = 0; j < face.size(); ++j) {  // checked before anything changes: the kernels index with these
-    const WallFace& w = wall_faces[face[j]];
-    if (w.cell >= N || w.slot >= wf) throw std::logic_error("surface: wall face outside the face-slot arrays");
-    cell[j] = w.cell;
-    slot[j] = w.slot;
+  std::vector<uint32_t> sel = wall_faces_in_box(wall, x0, y0, x1, y1);
+  const uint32_t wf = (uint32_t)flow.fs.wf;
+  std::vector<uint32_t> hcell(sel.size()), hslot(sel.size());
+  for (size_t j = 0; j < sel.size(); ++j) {  // checked before anything changes: the kernels index with these
+    const WallFace& w = wall[sel[j]];
+    if (w.cell >= flow.N || w.slot >= wf) throw std::logic_error("surface: wall face outside the face-slot arrays");
+    hcell[j] = w.cell;
+    hslot[j] = w.slot;
   }
-  const bool stats = sf_on && sf_stats;  // a new surface keeps the statistics on, and resets them
-  surface_clear();
-  sf_cell = sf_arena.upload(cell, stream);
-  sf_slot = sf_arena.upload(slot, stream);
-  sync();  // the uploads read host vectors that end here
-  sf_face.swap(face);
-  sf_ld = std::max<size_t>(64, (sf_face.size() + 63) / 64 * 64);
-  sf_stats = stats;
-  sf_on = true;
-  surface_derive();
-  return (uint32_t)sf_face.size();
+  const bool keep_stats = on && stats;  // a new surface keeps the statistics on, and resets them
+  clear(flow);
+  cell = arena.upload(hcell, flow.stream);
+  slot = arena.upload(hslot, flow.stream);
+  flow.sync();  // the uploads read host vectors that end here
+  face.swap(sel);
+  ld = std::max<size_t>(64, (face.size() + 63) / 64 * 64);
+  stats = keep_stats;
+  on = true;
+  derive(flow);
+  return (uint32_t)face.size();
 }
 
-void Solver::surface_geometry(uint32_t* cell, uint32_t* slot, double* cx, double* cy, double* nx, double* ny, double* area,
-                              double* dist_e) {
-  surface_need("cfd_surface_geometry_get");
-  for (size_t j = 0; j < sf_face.size(); ++j) {
-    const WallFace& w = wall_faces[sf_face[j]];
-    const size_t e = (size_t)w.slot * N + w.cell;  // the f32 values the kernels read
-    if (cell) cell[j] = w.cell;
-    if (slot) slot[j] = w.slot;
+void SurfaceDist::geometry(const FlowView& flow, const std::vector<WallFace>& wall, const Topology& topo,
+                           uint32_t* cell_out, uint32_t* slot_out, double* cx, double* cy, double* nx, double* ny,
+                           double* area, double* dist_e) {
+  need(flow, "cfd_surface_geometry_get");
+  for (size_t j = 0; j < face.size(); ++j) {
+    const WallFace& w = wall[face[j]];
+    const size_t e = (size_t)w.slot * flow.N + w.cell;  // the f32 values the kernels read
+    if (cell_out) cell_out[j] = w.cell;
+    if (slot_out) slot_out[j] = w.slot;
     if (cx) cx[j] = w.cx;
     if (cy) cy[j] = w.cy;
     if (nx) nx[j] = (double)topo.fs_nx[e];
@@ -102,115 +100,105 @@ void Solver::surface_geometry(uint32_t* cell, uint32_t* slot, double* cx, double
   }
 }
 
-void Solver::surface_info(cfd_surface_info* out) {
-  surface_need("cfd_surface_info_get");
-  std::memset(out, 0, sizeof(*out));
-  out->faces = (uint32_t)sf_face.size();
-  out->channels = sf_nch;
-  out->samples = sf_samples;
-  out->total_weight = sf_W;
-  out->stats_on = sf_stats ? 1 : 0;
+void SurfaceDist::info(const FlowView& flow, cfd_surface_info* info_out) {
+  need(flow, "cfd_surface_info_get");
+  std::memset(info_out, 0, sizeof(*info_out));
+  info_out->faces = (uint32_t)face.size();
+  info_out->channels = nch;
+  info_out->samples = samples;
+  info_out->total_weight = W;
+  info_out->stats_on = stats ? 1 : 0;
 }
 
-SurfaceArgs Solver::surface_args() {
+SurfaceArgs SurfaceDist::args(const FlowView& flow) const {
   SurfaceArgs a{};
-  a.n = (uint32_t)sf_face.size();
-  a.N = N;
-  a.nf = (uint32_t)sc_count;
-  a.cell = sf_cell;
-  a.slot = sf_slot;
-  a.c = constants;
-  a.u = S().u;
-  a.p = S().p;
-  a.area = fs.area;
-  a.nx = fs.nx;
-  a.ny = fs.ny;
-  a.dist_e = fs.dist_e;
-  a.wf = (uint32_t)fs.wf;
-  for (int f = 0; f < sc_count; ++f) {
-    const ScalarField& s = sc_field[f];
-    SurfaceField& d = a.f[f];
-    d.phi = s.phi;
-    d.sel = s.wall_on() ? s.sel : nullptr;  // scalar_wall_flux's own condition
-    d.rd = constants.density * s.par.diffusivity;
-    d.kind = s.wall.kind;
-    d.value = s.wall.value;
-  }
-  a.ld = sf_ld;
-  a.out = sf_out;
-  a.mean = sf_mean;
-  a.m2 = sf_m2;
+  a.n = (uint32_t)face.size();
+  a.N = flow.N;
+  a.nf = (uint32_t)flow.nf;
+  a.cell = cell;
+  a.slot = slot;
+  a.c = flow.constants;
+  a.u = flow.u;
+  a.p = flow.p;
+  a.area = flow.fs.area;
+  a.nx = flow.fs.nx;
+  a.ny = flow.fs.ny;
+  a.dist_e = flow.fs.dist_e;
+  a.wf = (uint32_t)flow.fs.wf;
+  for (int f = 0; f < flow.nf; ++f) a.f[f] = flow.field[f];
+  a.ld = ld;
+  a.out = out;
+  a.mean = mean;
+  a.m2 = m2;
   return a;
 }
 
-void Solver::surface_sample(double* out) {
-  surface_need("cfd_surface_sample");
-  const size_t n = sf_face.size();
+void SurfaceDist::sample(const FlowView& flow, double* sample_out) {
+  need(flow, "cfd_surface_sample");
+  const size_t n = face.size();
   if (n == 0) return;
   const Range range("surface sample");
-  CFD_HIP(hipSetDevice(device));
-  const SurfaceArgs a = surface_args();
-  const BcvArgs bcv = bcv_args();
-  launch_surface_sample(a, bcv_on() ? &bcv : nullptr, stream);
-  check_launch("surface sample");
-  CFD_HIP(hipMemcpy2DAsync(out, n * sizeof(double), sf_out, sf_ld * sizeof(double), n * sizeof(double), sf_nch,
-                           hipMemcpyDeviceToHost, stream));
-  sync();
+  CFD_HIP(hipSetDevice(flow.device));
+  const SurfaceArgs a = args(flow);
+  launch_surface_sample(a, flow.bcv(), flow.stream);
+  flow.check_launch("surface sample");
+  CFD_HIP(hipMemcpy2DAsync(sample_out, n * sizeof(double), out, ld * sizeof(double), n * sizeof(double), nch,
+                           hipMemcpyDeviceToHost, flow.stream));
+  flow.sync();
 }
 
-void Solver::surface_stats_enable(bool on) {
-  surface_need("cfd_surface_stats_enable");
-  if (on == sf_stats) return;
-  sf_stats = on;
-  surface_derive();
+void SurfaceDist::stats_enable(const FlowView& flow, bool enable) {
+  need(flow, "cfd_surface_stats_enable");
+  if (enable == stats) return;
+  stats = enable;
+  derive(flow);
 }
 
-void Solver::surface_stats_reset() {
-  surface_need("cfd_surface_stats_reset");
-  if (!sf_stats) throw std::invalid_argument("cfd_surface_stats_reset: surface statistics are not enabled (cfd_surface_stats_enable)");
-  CFD_HIP(hipSetDevice(device));
-  const size_t len = (size_t)sf_nch * sf_ld;
-  CFD_HIP(hipMemsetAsync(sf_mean, 0, len * sizeof(double), stream));
-  CFD_HIP(hipMemsetAsync(sf_m2, 0, len * sizeof(double), stream));
-  sf_W = 0.0;
-  sf_samples = 0;
+void SurfaceDist::stats_reset(const FlowView& flow) {
+  need(flow, "cfd_surface_stats_reset");
+  if (!stats) throw std::invalid_argument("cfd_surface_stats_reset: surface statistics are not enabled (cfd_surface_stats_enable)");
+  CFD_HIP(hipSetDevice(flow.device));
+  const size_t len = (size_t)nch * ld;
+  CFD_HIP(hipMemsetAsync(mean, 0, len * sizeof(double), flow.stream));
+  CFD_HIP(hipMemsetAsync(m2, 0, len * sizeof(double), flow.stream));
+  W = 0.0;
+  samples = 0;
 }
 
-void Solver::surface_stats_accumulate(double weight) {
-  surface_need("cfd_surface_stats_accumulate");
-  if (!sf_stats)
+void SurfaceDist::stats_accumulate(const FlowView& flow, double weight) {
+  need(flow, "cfd_surface_stats_accumulate");
+  if (!stats)
     throw std::invalid_argument("cfd_surface_stats_accumulate: surface statistics are not enabled (cfd_surface_stats_enable)");
   if (!std::isfinite(weight)) throw std::invalid_argument("cfd_surface_stats_accumulate: the weight must be finite");
   if (!(weight > 0.0)) {
-    if (!(last_step_dt > 0.0f))
+    if (!(flow.last_step_dt > 0.0f))
       throw std::invalid_argument("cfd_surface_stats_accumulate: weight <= 0 asks for the dt of the last cfd_step, and there was none");
-    weight = (double)last_step_dt;
+    weight = (double)flow.last_step_dt;
   }
   const Range range("surface statistics");
-  CFD_HIP(hipSetDevice(device));
-  const double Wn = sf_W + weight;
-  SurfaceArgs a = surface_args();
+  CFD_HIP(hipSetDevice(flow.device));
+  const double Wn = W + weight;
+  SurfaceArgs a = args(flow);
   a.w = weight;
   a.r = weight / Wn;
-  const BcvArgs bcv = bcv_args();
-  launch_surface_accumulate(a, bcv_on() ? &bcv : nullptr, stream);
-  check_launch("surface statistics");
-  sf_W = Wn;
-  sf_samples += 1;
+  launch_surface_accumulate(a, flow.bcv(), flow.stream);
+  flow.check_launch("surface statistics");
+  W = Wn;
+  samples += 1;
 }
 
-void Solver::surface_stats_get(int kind, double* out) {
-  surface_need("cfd_surface_stats_get");
-  if (!sf_stats) throw std::invalid_argument("cfd_surface_stats_get: surface statistics are not enabled (cfd_surface_stats_enable)");
+void SurfaceDist::stats_get(const FlowView& flow, int kind, double* stats_out) {
+  need(flow, "cfd_surface_stats_get");
+  if (!stats) throw std::invalid_argument("cfd_surface_stats_get: surface statistics are not enabled (cfd_surface_stats_enable)");
   if (kind != 0 && kind != 1) throw std::invalid_argument("cfd_surface_stats_get: kind must be 0 (mean) or 1 (variance)");
-  const size_t n = sf_face.size();
+  const size_t n = face.size();
   if (n == 0) return;
-  CFD_HIP(hipSetDevice(device));
-  CFD_HIP(hipMemcpy2DAsync(out, n * sizeof(double), kind == 0 ? sf_mean : sf_m2, sf_ld * sizeof(double), n * sizeof(double),
-                           sf_nch, hipMemcpyDeviceToHost, stream));
-  sync();
-  if (kind == 1 && sf_W > 0.0)  // W == 0: every M2 is +0 and stays
-    for (size_t q = 0; q < (size_t)sf_nch * n; ++q) out[q] = out[q] / sf_W;
+  CFD_HIP(hipSetDevice(flow.device));
+  CFD_HIP(hipMemcpy2DAsync(stats_out, n * sizeof(double), kind == 0 ? mean : m2, ld * sizeof(double), n * sizeof(double),
+                           nch, hipMemcpyDeviceToHost, flow.stream));
+  flow.sync();
+  if (kind == 1 && W > 0.0)  // W == 0: every M2 is +0 and stays
+    for (size_t q = 0; q < (size_t)nch * n; ++q) stats_out[q] = stats_out[q] / W;
 }
 
 }  // namespace cfd2
