@@ -88,7 +88,7 @@ double Solver::layout_step_bytes() const {
   const int M = cfg.fixed_inner > 0 ? std::min(cfg.fixed_inner, m) : m;
   const double prep = 40 * S + 60 * Nn;                    // 9 slot arrays + flux out; cell state in, gradients out
   BuoyancyArgs bu;
-  const double buoy = buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // the buoyant assembly: one field value per driving field
+  const double buoy = scalars.buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // the buoyant assembly: one field value per driving field
   const double asmb = 32 * S + 20 * Sint + 78 * Nn + buoy; // 8 slot arrays; 3x3 block + Poisson entry out
   const double spmv = (35 + 16 * ws) * Nn;                 // headers, cval_a + cval_g slots, x, y
   const double predict = (39 + 8 * ws) * Nn;               // headers, cval_g slots, V_j, dinv, temp_p / p_sol out
@@ -111,7 +111,7 @@ double Solver::algorithmic_step_bytes() const {
   const double nnz_s = S;
   const double prep = 84 * Nn + 4 * Sfaces + 36 * Fn;
   BuoyancyArgs bu;
-  const double buoy = buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // as in layout_step_bytes
+  const double buoy = scalars.buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // as in layout_step_bytes
   const double asmb = 68 * Nn + 8 * Sfaces + 36 * Fn + 40 * nnz_s + buoy;
   const int K = cfg.fixed_outer > 0 ? cfg.fixed_outer : std::max(cfg.n_outer_correctors, 10);
   const int M = cfg.fixed_inner > 0 ? std::min(cfg.fixed_inner, m) : m;

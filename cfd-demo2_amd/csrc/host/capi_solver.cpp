@@ -561,35 +561,31 @@ cfd_status cfd_scalars_enable(cfd_solver* s, int32_t count, const cfd_scalar_con
     c = *cfg;
   else
     cfd_scalar_config_default(&c);
-  return guard([&] { s->s->scalars_enable(count, c); });
+  return guard([&] { s->s->scalars.enable(s->s->view(nullptr), count, c); });
 }
 cfd_status cfd_set_scalar_params(cfd_solver* s, int32_t field, const cfd_scalar_params* p) {
   CHECK_S(s);
   if (!p) return set_error(CFD_ERR_INVALID, "null scalar params");
-  return guard([&] {
-    s->s->scalar_check(field);
-    if (!(p->diffusivity >= 0.0f)) throw std::invalid_argument("scalar diffusivity must be >= 0");
-    s->s->sc_field[field].par = *p;
-  });
+  return guard([&] { s->s->scalars.set_params(s->s->view(nullptr), field, *p); });
 }
 cfd_status cfd_set_scalar(cfd_solver* s, int32_t field, const double* phi) {
   CHECK_S(s);
   if (!phi) return set_error(CFD_ERR_INVALID, "null phi");
-  return guard([&] { s->s->set_scalar(field, phi); });
+  return guard([&] { s->s->scalars.set(s->s->view(nullptr), field, phi); });
 }
 cfd_status cfd_get_scalar(cfd_solver* s, int32_t field, double* phi) {
   CHECK_S(s);
   if (!phi) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->get_scalar(field, phi); });
+  return guard([&] { s->s->scalars.get(s->s->view(nullptr), field, phi); });
 }
 cfd_status cfd_scalar_advance(cfd_solver* s, float dt) {
   CHECK_S(s);
-  return guard([&] { s->s->scalar_advance(dt); });
+  return guard([&] { s->s->scalars.advance(s->s->view(nullptr), dt); });
 }
 cfd_status cfd_scalar_stats_get(cfd_solver* s, int32_t field, cfd_scalar_stats* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->scalar_stats(field, out); });
+  return guard([&] { s->s->scalars.stats(s->s->view(nullptr), field, out); });
 }
 void cfd_scalar_solver_default(cfd_scalar_solver* c) {
   if (!c) return;
@@ -601,17 +597,12 @@ void cfd_scalar_solver_default(cfd_scalar_solver* c) {
 cfd_status cfd_set_scalar_solver(cfd_solver* s, int32_t field, const cfd_scalar_solver* cfg) {
   CHECK_S(s);
   if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar solver config");
-  return guard([&] { s->s->set_scalar_solver(field, *cfg); });
+  return guard([&] { s->s->scalars.set_solver(s->s->view(nullptr), field, *cfg); });
 }
 cfd_status cfd_scalar_solver_stats_get(cfd_solver* s, int32_t field, cfd_scalar_solver_stats* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] {
-    if (s->s->dist())
-      throw std::invalid_argument("passive scalars run on one GPU only: no scalar solver on a distributed handle");
-    s->s->scalar_check(field);
-    *out = s->s->sc_field[field].kstats;
-  });
+  return guard([&] { s->s->scalars.solver_stats(s->s->view(nullptr), field, out); });
 }
 void cfd_scalar_scheme_default(cfd_scalar_scheme* c) {
   if (!c) return;
@@ -620,18 +611,19 @@ void cfd_scalar_scheme_default(cfd_scalar_scheme* c) {
 cfd_status cfd_set_scalar_scheme(cfd_solver* s, int32_t field, const cfd_scalar_scheme* cfg) {
   CHECK_S(s);
   if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar scheme config");
-  return guard([&] { s->s->set_scalar_scheme(field, *cfg); });
+  return guard([&] { s->s->scalars.set_scheme(s->s->view(nullptr), field, *cfg); });
 }
 cfd_status cfd_scalar_scheme_stats_get(cfd_solver* s, int32_t field, cfd_scalar_scheme_stats* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->scalar_scheme_stats(field, out); });
+  return guard([&] { s->s->scalars.scheme_stats(s->s->view(nullptr), field, out); });
 }
 cfd_status cfd_set_scalar_wall(cfd_solver* s, int32_t field, const cfd_scalar_wall* cfg, uint32_t* faces) {
   CHECK_S(s);
   if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar wall config");
   return guard([&] {
-    const uint32_t n = s->s->set_scalar_wall(field, *cfg);
+    cfd2::Solver& S = *s->s;
+    const uint32_t n = S.scalars.set_wall(S.view(nullptr), S.wall_faces, S.cell_cx, S.cell_cy, field, *cfg);
     if (faces) *faces = n;
   });
 }
@@ -639,33 +631,34 @@ cfd_status cfd_set_scalar_source(cfd_solver* s, int32_t field, const cfd_scalar_
   CHECK_S(s);
   if (!cfg) return set_error(CFD_ERR_INVALID, "null scalar source config");
   return guard([&] {
-    const uint32_t n = s->s->set_scalar_source(field, *cfg);
+    cfd2::Solver& S = *s->s;
+    const uint32_t n = S.scalars.set_source(S.view(nullptr), S.wall_faces, S.cell_cx, S.cell_cy, field, *cfg);
     if (cells) *cells = n;
   });
 }
 cfd_status cfd_scalar_wall_flux_get(cfd_solver* s, int32_t field, cfd_scalar_wall_flux* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->scalar_wall_flux(field, out); });
+  return guard([&] { s->s->scalars.wall_flux(s->s->view(nullptr), field, out); });
 }
 cfd_status cfd_set_scalar_buoyancy(cfd_solver* s, int32_t field, float beta, float ref) {
   CHECK_S(s);
-  return guard([&] { s->s->set_buoyancy(field, beta, ref); });
+  return guard([&] { s->s->scalars.set_buoyancy(s->s->view(nullptr), field, beta, ref); });
 }
 cfd_status cfd_set_gravity(cfd_solver* s, float gx, float gy) {
   CHECK_S(s);
-  return guard([&] { s->s->set_gravity(gx, gy); });
+  return guard([&] { s->s->scalars.set_gravity(s->s->view(nullptr), gx, gy); });
 }
 cfd_status cfd_buoyancy_get(const cfd_solver* s, cfd_buoyancy* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  s->s->buoyancy_get(out);
+  s->s->scalars.buoyancy_get(s->s->view(nullptr), out);
   return CFD_OK;
 }
 cfd_status cfd_buoyancy_force_get(cfd_solver* s, cfd_buoyancy_force* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->buoyancy_force(out); });
+  return guard([&] { s->s->scalars.buoyancy_force(s->s->view(nullptr), out); });
 }
 
 // -------------------------------------------- prescribed boundary velocities
@@ -674,24 +667,32 @@ cfd_status cfd_set_boundary_velocity(cfd_solver* s, uint32_t n, const uint32_t* 
   CHECK_S(s);
   if (n && (!face_ids || !vx || !vy)) return set_error(CFD_ERR_INVALID, "null face_ids / vx / vy");
   return guard([&] {
-    const uint32_t c = s->s->set_boundary_velocity(n, face_ids, vx, vy);
+    s->s->bcv_need("boundary velocity");
+    const uint32_t c = s->s->bcv.set(s->s->view(nullptr), n, face_ids, vx, vy);
     if (selected) *selected = c;
   });
 }
 cfd_status cfd_set_boundary_velocity_scale(cfd_solver* s, float inlet_scale, float wall_scale) {
   CHECK_S(s);
-  return guard([&] { s->s->set_boundary_velocity_scale(inlet_scale, wall_scale); });
+  return guard([&] {
+    s->s->bcv_need("boundary velocity scale");
+    s->s->bcv.set_scale(s->s->view(nullptr), inlet_scale, wall_scale);
+  });
 }
 cfd_status cfd_boundary_velocity_get(const cfd_solver* s, cfd_boundary_velocity* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  s->s->boundary_velocity_get(out);
+  s->s->bcv.get(s->s->view(nullptr), out);
   return CFD_OK;
 }
 cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_motion* out) {
   CHECK_S(s);
   if (!out) return set_error(CFD_ERR_INVALID, "null out");
-  return guard([&] { s->s->wall_motion(x0, y0, out); });
+  return guard([&] {
+    cfd2::Solver& S = *s->s;
+    S.bcv_need("wall motion");
+    S.bcv.wall_motion(S.view(nullptr), S.region, S.wall_faces, x0, y0, out);
+  });
 }
 
 // ------------------------------------------------------- frames on the device

@@ -13,7 +13,7 @@ void Solver::set_reference_semantics(int flags) {
     throw std::invalid_argument("reference semantics on the GPU: flags 1 (in-place smoother), 2 (racy prepare), "
                                 "4 (reduction order), 8 (restrict clamp) only");
   if (flags && dist()) throw std::invalid_argument("reference semantics: one GPU only");
-  if ((flags & 2) && bcv_on())
+  if ((flags & 2) && bcv.on())
     throw std::invalid_argument("reference semantics: the racy prepare has no form with prescribed boundary velocities "
                                 "(clear them first)");
   if ((flags & 2) && !d_flux_mirror) {  // each non-owner face slot -> the owner's slot of that face

@@ -51,15 +51,15 @@ void Solver::flow_diag_device(bool fields, bool reduce) {
   a.vol = d_vol;
   a.u = S().u;
   a.p = S().p;
-  a.wall_mask = region_on ? diag_mask : nullptr;
+  a.wall_mask = region.on ? region.mask : nullptr;
   a.omega_out = fields ? diag_omega : nullptr;
   a.div_out = fields ? diag_div : nullptr;
-  a.out = sum_out(diag_partial);
+  a.out = sums().out(diag_partial);
   a.blockmax = diag_blockmax;
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(diag_res + 6);
   // prescribed boundary velocities: the moving walls' face values and relative velocity
-  const BcvArgs bcv = bcv_args();
-  launch_flow_diag(a, bcv_on() ? &bcv : nullptr, mx, stream);
+  const BcvArgs v = bcv.args();
+  launch_flow_diag(a, bcv.on() ? &v : nullptr, mx, stream);
   if (!reduce) {  // derived fields only: nothing to reduce across ranks, not collective
     check_launch("flow diagnostics (fields)");
     return;
@@ -107,7 +107,7 @@ void Solver::flow_diagnostics(cfd_flow_diag* out, bool fields) {
   const uint64_t* src = dist() ? h.data() + 9 : h.data() + 6;
   for (int q = 0; q < R; ++q)  // rank order (a maximum of bit patterns: any order gives the same)
     for (int j = 0; j < 3; ++j) m[j] = std::max(m[j], src[3 * q + j]);
-  flow_diag_decode(h.data(), m, region_faces, out);
+  flow_diag_decode(h.data(), m, region.faces, out);
 }
 
 void Solver::get_derived(int kind, double* out) {
@@ -128,16 +128,6 @@ void Solver::get_derived(int kind, double* out) {
   for (uint32_t i = 0; i < N; ++i) out[i] = f[i];
 }
 
-std::vector<uint32_t> wall_faces_in_box(const std::vector<WallFace>& wall, double x0, double y0, double x1, double y1) {
-  std::vector<uint32_t> sel;
-  if (x1 < x0) return sel;
-  for (size_t j = 0; j < wall.size(); ++j) {
-    const WallFace& wfc = wall[j];
-    if (wfc.cx >= x0 && wfc.cx <= x1 && wfc.cy >= y0 && wfc.cy <= y1) sel.push_back((uint32_t)j);
-  }
-  return sel;
-}
-
 uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
   CFD_HIP(hipSetDevice(device));
   std::vector<uint16_t> mask;
@@ -150,14 +140,14 @@ uint32_t Solver::set_force_region(double x0, double y0, double x1, double y1) {
     if (mask.empty()) mask.assign(N, 0);
     mask[wfc.cell - topo.c0] |= (uint16_t)(1u << wfc.slot);
   }
-  region_faces = count;
-  ++region_gen;  // wall_motion rebuilds its table of face centres
-  region_box[0] = x0, region_box[1] = y0, region_box[2] = x1, region_box[3] = y1;
-  region_on = count != 0;  // every rank runs the same kernel form (the force sums of a rank without faces are +0)
-  if (!region_on) return 0;
+  region.faces = count;
+  ++region.gen;  // wall_motion rebuilds its table of face centres
+  region.box[0] = x0, region.box[1] = y0, region.box[2] = x1, region.box[3] = y1;
+  region.on = count != 0;  // every rank runs the same kernel form (the force sums of a rank without faces are +0)
+  if (!region.on) return 0;
   if (mask.empty()) mask.assign(N, 0);
-  if (!diag_mask) diag_mask = arena.alloc<uint16_t>(N);
-  CFD_HIP(hipMemcpyAsync(diag_mask, mask.data(), (size_t)N * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
+  if (!region.mask) region.mask = arena.alloc<uint16_t>(N);
+  CFD_HIP(hipMemcpyAsync(region.mask, mask.data(), (size_t)N * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
   sync();
   return count;
 }
@@ -186,7 +176,7 @@ void Solver::monitor_record() {
   const Range range("monitor record");
   CFD_HIP(hipSetDevice(device));
   if (monitor.diag) flow_diag_device(false, true);
-  monitor.record(flow, diag_res, region_faces);
+  monitor.record(flow, diag_res, region);
 }
 
 float Solver::adapt_dt(double target_cfl) {

@@ -132,16 +132,11 @@ void Solver::comm_prof_reset() {
 // the segment values, and every rank finishes the same global tree.
 template <class T>
 RedSrcT<T> Solver::combine(const T* part, int nvec, T* local, T* gather) {
+  if (!dist()) return sums().src(part, nvec);
   RedSrcT<T> r;
   r.G = red.G / red.U;  // units per segment
   r.nseg = red.nseg;
   r.nvec = (uint32_t)nvec;
-  if (!dist()) {
-    r.p = part;
-    r.stride = pstride;
-    r.nchunks = nunits;
-    return r;
-  }
   if constexpr (std::is_same<T, double>::value) {
     if (!local) {
       local = red_local_d;

@@ -129,9 +129,9 @@ struct Monitor {
   void disable(const FlowView& flow);
   // record in two halves (Solver::monitor_record runs the flow diagnostics
   // between them when diag is set): the checks, then the launch.  diag_res: the
-  // diagnostics' device result; region_faces: the force region's face count.
+  // diagnostics' device result over `region`.
   void record_check(const FlowView& flow) const;
-  void record(const FlowView& flow, const uint64_t* diag_res, uint32_t region_faces);
+  void record(const FlowView& flow, const uint64_t* diag_res, const ForceRegion& region);
   void get(const FlowView& flow, uint64_t first, uint64_t count, float* time_out, float* dt, float* probes,
            cfd_flow_diag* diag_out);
   void count(const FlowView& flow, uint64_t* total_out, uint64_t* held) const;  // each may be null

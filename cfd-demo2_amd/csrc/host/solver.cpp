@@ -61,13 +61,9 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
       if (f >= mesh.num_faces) throw std::invalid_argument("cell_faces out of range");
       if (mesh.face_neighbor[f] == UINT32_MAX && (mesh.face_boundary[f] & 3u) == 3u)
         wall_faces.push_back({mesh.face_cx[f], mesh.face_cy[f], i, k - mesh.cell_face_offsets[i]});
-      const uint32_t bt = mesh.face_boundary[f] & 3u;
-      if (R == 1 && mesh.face_neighbor[f] == UINT32_MAX && (bt == 1u || bt == 3u))  // boundary_velocity.cpp
-        bnd_faces.push_back({f, i, k - mesh.cell_face_offsets[i], bt, mesh.face_nx[f], mesh.face_ny[f],
-                             mesh.face_cx[f], mesh.face_cy[f]});
     }
-  std::sort(bnd_faces.begin(), bnd_faces.end(), [](const BndFace& a, const BndFace& b) { return a.face < b.face; });
-  if (R == 1) {  // passive scalars (one GPU only): the source box tests the f64 centres
+  if (R == 1) {  // the opt-in physics (one GPU only): boundary faces; the source box tests the f64 centres
+    bcv.faces = boundary_faces(mesh);
     cell_cx.assign(mesh.cell_cx, mesh.cell_cx + NG);
     cell_cy.assign(mesh.cell_cy, mesh.cell_cy + NG);
   }
@@ -213,21 +209,14 @@ Solver::Solver(const cfd_mesh_view& mesh, const cfd_config& c, int dev, std::uni
 }
 
 FlowView Solver::view(const char* one_gpu_message) const {
-  if (dist()) throw std::invalid_argument(one_gpu_message);
-  auto field = [&](int f) {
-    SurfaceField d{};
-    if (f >= sc_count) return d;
-    const ScalarField& s = sc_field[f];
-    d.phi = s.phi;
-    d.sel = s.wall_on() ? s.sel : nullptr;  // scalar_wall_flux's own condition
-    d.rd = constants.density * s.par.diffusivity;
-    d.kind = s.wall.kind;
-    d.value = s.wall.value;
-    return d;
-  };
-  return FlowView{device,   stream,   N,        NG,       fs,           constants,  ring[i_state].u, ring[i_state].p,
-                  sc_count, {field(0), field(1), field(2), field(3)},   last_step_dt, bcv_args(),    bcv_on(),
-                  surface_gen, check_sync};
+  if (one_gpu_message && dist()) throw std::invalid_argument(one_gpu_message);
+  auto field = [&](int f) { return scalars.surface_field(f, constants.density); };
+  return FlowView{device,           stream,           dist(),          N,
+                  NG,               topo.ld,          fs,              d_vol,
+                  flux_s,           sums(),           constants,       ring[i_state].u,
+                  ring[i_state].p,  scalars.s.count,  {field(0), field(1), field(2), field(3)},
+                  last_step_dt,     bcv.args(),       bcv.on(),        scalars.gen + bcv.gen,
+                  check_sync};
 }
 
 Solver::~Solver() {
@@ -247,10 +236,10 @@ Solver::~Solver() {
   if (hev_done) (void)hipEventDestroy(hev_done);
   comm.reset();
   arena.release();
-  bcv_arena.release();
-  wm_arena.release();
+  bcv.arena.release();
+  bcv.wm_arena.release();
   amg_arena.release();
-  sc_arena.release();
+  scalars.arena.release();
   if (cstream) (void)hipStreamDestroy(cstream);
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -369,8 +358,8 @@ void Solver::prepare() {
     check_launch("prepare (reference semantics)");
     return;
   }
-  if (bcv_on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
-    launch_prepare_bcv(a, bcv_args(), stream);
+  if (bcv.on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
+    launch_prepare_bcv(a, bcv.args(), stream);
   else
     launch_prepare(a, stream);
   check_launch("prepare");
@@ -406,9 +395,9 @@ void Solver::assemble() {
   // Boussinesq buoyancy (scalar.cpp): the buoyant form only when a field drives
   // and g != 0; otherwise the plain kernel with the arguments it always had
   BuoyancyArgs b;
-  const bool buoyant = buoyancy_args(b);
-  if (bcv_on())  // prescribed boundary velocities: the BCV form of either
-    launch_assemble_bcv(a, buoyant ? &b : nullptr, bcv_args(), stream);
+  const bool buoyant = scalars.buoyancy_args(b);
+  if (bcv.on())  // prescribed boundary velocities: the BCV form of either
+    launch_assemble_bcv(a, buoyant ? &b : nullptr, bcv.args(), stream);
   else if (buoyant)
     launch_assemble_buoyant(a, b, stream);
   else

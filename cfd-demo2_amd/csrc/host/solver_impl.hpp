@@ -14,10 +14,12 @@
 #include "../../../include/cfd2_amd.h"
 #include "../hip/amg_setup.hpp"
 #include "../hip/kernels.hpp"
+#include "boundary_velocity.hpp"
 #include "comm.hpp"
 #include "device_mem.hpp"
 #include "dist.hpp"
 #include "modules.hpp"
+#include "scalars.hpp"
 #include "topology.hpp"
 #include "tuning.hpp"
 
@@ -252,7 +254,7 @@ constexpr uint64_t kAmgReplicateRowsDefault = 1u << 20;
 inline uint64_t amg_replicate_rows() { return knob_u64(Knob::AmgReplicateRows, kAmgReplicateRowsDefault); }
 
 struct Solver {
- public:  // what the C API, checkpoint.cpp, scalar.cpp and diagnostics.cpp touch, by owning file
+ public:  // what the C API, checkpoint.cpp and diagnostics.cpp touch, by owning file
   // ---- solver.cpp: construction, state API, step ----
   cfd_config cfg{};
   int device = 0;
@@ -331,29 +333,8 @@ struct Solver {
   // FGMRES iteration's for float, check_evolution's 5 vectors for double)
   template <class T>
   RedSrcT<T> combine(const T* part, int nvec, T* local = nullptr, T* gather = nullptr);
-  // where a kernel with f64 cell sums leaves its unit partials (kernels.hpp SumOut)
-  SumOut sum_out(double* partial) const { return SumOut{red.U, pstride, partial}; }
-  // The work space of a read-only diagnostic with ns such sums (one GPU): the
-  // unit partials and the ns totals, null before the first use.  sum_buf
-  // allocates them in `a` then and returns the kernel's destination; sum_read
-  // finishes the totals and reads them back into h[0, ns).
-  struct SumBuf {
-    double* partial = nullptr;  // [ns * pstride]
-    double* res = nullptr;      // [ns]
-  };
-  SumOut sum_buf(SumBuf& b, int ns, DeviceArena& a) {
-    if (!b.partial) {
-      b.partial = a.alloc<double>((size_t)ns * pstride);
-      b.res = a.alloc<double>(ns);
-    }
-    return sum_out(b.partial);
-  }
-  void sum_read(const SumBuf& b, int ns, double* h, const char* where) {
-    launch_evolution_final(combine(b.partial, ns), b.res, stream);
-    check_launch(where);
-    CFD_HIP(hipMemcpyAsync(h, b.res, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-    sync();
-  }
+  // the one-GPU geometry of those reductions, as the view carries it (flow_view.hpp)
+  CellSums sums() const { return CellSums{red.U, red.G / red.U, red.nseg, pstride, nunits}; }
   std::vector<uint64_t> allgather_u64(uint64_t mine);  // every rank's value (collective)
   // ---- timing of the distributed communication (cfd_comm_timing) ----
   // While comm_prof is on, every halo exchange and all-gather of the step is
@@ -465,9 +446,7 @@ struct Solver {
   double* diag_red_gather = nullptr;
   float* diag_omega = nullptr;       // [N] field outputs (first cfd_get_derived)
   float* diag_div = nullptr;
-  uint16_t* diag_mask = nullptr;     // [N] selected wall slots (first non-empty force region)
-  bool region_on = false;
-  uint32_t region_faces = 0;         // selected wall faces, whole mesh
+  ForceRegion region;                // set_force_region fills it (topology.hpp)
   void flow_diagnostics(cfd_flow_diag* out, bool fields = false);
   // its device half: the launches that leave the sums and maxima in diag_res
   // (reduce false: the pass alone, for the derived fields); flow_diag_decode
@@ -477,125 +456,16 @@ struct Solver {
   void get_derived(int kind, double* out);
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
-  // ---- passive scalars (scalar.cpp; kernels.hpp "scalar.hip") ----
-  // Opt-in: nothing below is allocated before scalars_enable, and step()
-  // launches none of it; step() only records the dt it used (last_step_dt).
-  // One GPU only.  Every buffer lives in sc_arena, released by
-  // scalars_enable(0).
-  struct ScalarField {
-    float* phi = nullptr;  // [ld] the current iterate (swaps with sc_alt during an advance)
-    cfd_scalar_params par{};
-    uint32_t sweeps = 0;
-    int32_t converged = 0;
-    float last_delta = 0.0f;
-    float dt_used = 0.0f;
-    cfd_scalar_solver solver{0, 500, 8, 0};  // cfd_scalar_solver_default
-    cfd_scalar_solver_stats kstats{};        // of the last advance
-    int32_t scheme = 0;                      // cfd_scalar_scheme.scheme, for the next advance
-    int32_t scheme_used = 0;                 // of the last advance
-    uint32_t clamped = 0;                    // of the last advance (copied from hr_count during it)
-    // wall condition and source (cfd_set_scalar_wall / cfd_set_scalar_source), for the next advance
-    cfd_scalar_wall wall{};                  // kind 0: every wall adiabatic
-    cfd_scalar_source source{};              // rate 0: none
-    uint32_t wall_n = 0;                     // wall faces in wall's box
-    uint32_t source_n = 0;                   // cells in source's box
-    uint32_t* sel = nullptr;                 // [N] the selection image (kernels.hpp ScalarBC), null before the first non-trivial selection
-    // Boussinesq buoyancy (set_buoyancy): the field drives the momentum equation when beta != 0
-    float beta = 0.0f;
-    float bref = 0.0f;
-    bool wall_on() const { return wall.kind != 0 && wall_n != 0; }
-    bool source_on() const { return source.rate != 0.0f && source_n != 0; }
-  };
-  DeviceArena sc_arena;
-  int sc_count = 0;
-  cfd_scalar_config sc_cfg{};
-  ScalarField sc_field[4];
-  float* sc_alt = nullptr;         // [ld] ping-pong partner of the field being advanced
-  float* sc_coef = nullptr;        // [wf * ld] slot coefficients of the field being advanced
-  float* sc_diag = nullptr;        // [ld]
-  float* sc_b = nullptr;           // [ld]
-  uint32_t* sc_blockmax = nullptr; // per-block scratch of the sweep's delta and the stats' min / max
-  ScalarResults* sc_res = nullptr; // what the sweep and the statistics leave for the host
-  double* sc_partial = nullptr;    // [pstride] unit partials of the integral
-  // BiCGStab work space, allocated in sc_arena by the first set_scalar_solver
-  // that selects method 1 (null before)
-  float* kr_vec[6] = {};           // [ld] each: rh, r, p, v, s, t
-  double* kr_partial = nullptr;    // [2 * pstride] unit partials of an iteration's dots
-  ScalarKrylovState* kr_state = nullptr;
-  // Scheme 1 (limited linear) work space, allocated in sc_arena by the first
-  // set_scalar_scheme that selects it (null before)
-  float2* hr_grad = nullptr;       // [ld] the gradient of the phi_old being advanced
-  uint32_t* hr_count = nullptr;    // [4] clamped cells of each field's last scheme-1 assembly
-  // Wall-flux and buoyancy-force work space, allocated in sc_arena by the
-  // first scalar_wall_flux that has faces to sum over and the first
-  // buoyancy_force with buoyancy on
-  SumBuf wf_sums;                  // kWallFluxSums: flux, area, phi_area
-  SumBuf bf_sums;                  // kBuoyancySums
-  float gravity[2] = {0.0f, 0.0f}; // set_gravity; kept over scalars_enable (every beta is not)
-  std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: the source box)
-  float last_step_dt = 0.0f;       // the dt of the last step(); 0: no step yet
-  void scalars_enable(int count, const cfd_scalar_config& c);
-  void scalar_check(int field) const;  // throws std::invalid_argument: not enabled / bad index
-  void set_scalar(int field, const double* phi);
-  void get_scalar(int field, double* phi);
-  void scalar_advance(float dt);
-  void set_scalar_solver(int field, const cfd_scalar_solver& c);
-  void set_scalar_scheme(int field, const cfd_scalar_scheme& c);
-  void scalar_scheme_stats(int field, cfd_scalar_scheme_stats* out) const;
-  ScalarSystem scalar_system() const;   // the assembled system of the field being advanced (sc_coef, sc_diag, sc_b)
-  void scalar_krylov(ScalarField& f);   // the Krylov phase of one assembled field: f.phi becomes its frozen x
-  void scalar_polish(int fi, ScalarField& f);   // the Jacobi loop from f.phi: sweeps, last_delta, converged
-  void scalar_stats(int field, cfd_scalar_stats* out);
-  uint32_t set_scalar_wall(int field, const cfd_scalar_wall& c);      // returns the faces selected
-  uint32_t set_scalar_source(int field, const cfd_scalar_source& c);  // returns the cells selected
-  void scalar_select(ScalarField& f);   // f.sel from f.wall and f.source (allocates and uploads it when either is on)
-  void scalar_wall_flux(int field, cfd_scalar_wall_flux* out);
-  // Boussinesq buoyancy (include/cfd2_amd.h "Arithmetic of buoyancy"): explicit,
-  // one momentum source in the assembly, read from the fields as they stand
-  void set_buoyancy(int field, float beta, float ref);
-  void set_gravity(float gx, float gy);
-  // the driving fields (beta != 0, ascending) with their current pointers and
-  // g; true when the assembly takes its buoyant form (some entry and g != 0)
-  bool buoyancy_args(BuoyancyArgs& b) const;
-  void buoyancy_get(cfd_buoyancy* out) const;
-  void buoyancy_force(cfd_buoyancy_force* out);
-  // ---- prescribed boundary velocities (boundary_velocity.cpp; kernels.hpp BcvArgs) ----
-  // Opt-in: nothing below is allocated before the first non-empty
-  // set_boundary_velocity, and with an empty selection step() launches the
-  // kernels it always launched.  One GPU only; not in reference-semantics mode.
-  struct BndFace {      // every inlet and wall face of the mesh (one GPU), ascending face index
-    uint32_t face;
-    uint32_t cell, slot;
-    uint32_t btype;     // 1 inlet, 3 wall
-    double nx, ny;      // the f64 face normal (its sign does not matter here)
-    double cx, cy;      // the f64 face centre
-  };
-  struct BcvEntry {
-    float bx, by;
-    uint32_t btype;
-  };
-  std::vector<BndFace> bnd_faces;
-  std::vector<std::pair<uint32_t, BcvEntry>> bcv_sel;  // (index into bnd_faces, entry), ascending
-  DeviceArena bcv_arena;
-  uint32_t* bcv_dsel = nullptr;   // [N]; null: empty selection
-  float4* bcv_dtab = nullptr;     // [rows * wf]
-  float bcv_scale[2] = {1.0f, 1.0f};  // inlet, wall
-  double bcv_max_normal = 0.0;    // largest |v . n| removed from a wall entry of the current selection
-  bool bcv_on() const { return bcv_dsel != nullptr; }
-  BcvArgs bcv_args() const { return BcvArgs{bcv_dsel, bcv_dtab, bcv_scale[0], bcv_scale[1]}; }
-  void bcv_need(const char* what) const;  // throws: distributed, reference semantics
-  uint32_t set_boundary_velocity(uint32_t n, const uint32_t* faces, const float* vx, const float* vy);
-  void set_boundary_velocity_scale(float inlet_scale, float wall_scale);
-  void boundary_velocity_get(cfd_boundary_velocity* out) const;
-  // wall-motion sums over the force region: the compact table of the region's
-  // f64 face centres is rebuilt when the region changed (region_gen)
-  DeviceArena wm_arena;
-  uint32_t* wm_crow = nullptr;    // [N]
-  double2* wm_ctr = nullptr;      // [rows * wf]
-  SumBuf wm_sums;                 // kWallMotionSums, in wm_arena
-  uint64_t region_gen = 0, wm_gen = 0;  // set_force_region calls; the one wm_crow / wm_ctr were built for
-  double region_box[4] = {0, 0, -1, 0};
-  void wall_motion(double x0, double y0, cfd_wall_motion* out);
+  // ---- the opt-in physics (scalars.hpp, boundary_velocity.hpp) ----
+  // Each reads the solver through view() alone.  step() asks them for kernel
+  // arguments (scalars.buoyancy_args, bcv.on / bcv.args) and only records the
+  // dt it used (last_step_dt).
+  Scalars scalars;
+  BoundaryVelocity bcv;
+  std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: Scalars::set_source's box)
+  float last_step_dt = 0.0f;             // the dt of the last step(); 0: no step yet
+  // what BoundaryVelocity's calls refuse first: ref_racy stays private
+  void bcv_need(const char* what) const { BoundaryVelocity::need(what, dist(), ref_racy); }
   // ---- the opt-in post-processing modules (modules.hpp) ----
   // Each reads the solver through view() alone; nothing of theirs is allocated
   // before their first enabling call, and step() launches none of it.
@@ -604,9 +474,9 @@ struct Solver {
   TimeStats tstats;
   Monitor monitor;
   SurfaceDist surface;
-  uint64_t surface_gen = 0;  // scalars_enable, set_scalar_wall and set_boundary_velocity bump it (FlowView::surface_gen)
-  // The modules' view of this solver, built fresh for every call (the ring
-  // rotates); throws std::invalid_argument(one_gpu_message) on a distributed handle.
+  // The view of this solver, built fresh for every call (the ring rotates);
+  // throws std::invalid_argument(one_gpu_message) on a distributed handle,
+  // unless the message is null (the calls with words or no check of their own).
   FlowView view(const char* one_gpu_message) const;
   // the three module calls that need the flow diagnostics (diagnostics.cpp): a
   // frame of the vorticity or the divergence, and a monitor with diagnostics

@@ -190,11 +190,11 @@ void Monitor::record_check(const FlowView& flow) const {
                                 "monitor was enabled with " + std::to_string(ns) + " (cfd_monitor_enable again)");
 }
 
-void Monitor::record(const FlowView& flow, const uint64_t* diag_res, uint32_t region_faces) {
+void Monitor::record(const FlowView& flow, const uint64_t* diag_res, const ForceRegion& region) {
   record_check(flow);
   CFD_HIP(hipSetDevice(flow.device));
   const size_t slot = (size_t)(total % cap);
-  if (diag) faces[slot] = region_faces;
+  if (diag) faces[slot] = region.faces;
   MonitorRecordArgs a{};
   a.P = P;
   a.ns = ns;

@@ -298,4 +298,27 @@ void build_topology(const cfd_mesh_view& m, Topology& t, uint32_t c0, uint32_t c
   }
 }
 
+std::vector<uint32_t> wall_faces_in_box(const std::vector<WallFace>& wall, double x0, double y0, double x1, double y1) {
+  std::vector<uint32_t> sel;
+  if (x1 < x0) return sel;
+  for (size_t j = 0; j < wall.size(); ++j) {
+    const WallFace& wfc = wall[j];
+    if (wfc.cx >= x0 && wfc.cx <= x1 && wfc.cy >= y0 && wfc.cy <= y1) sel.push_back((uint32_t)j);
+  }
+  return sel;
+}
+
+std::vector<BndFace> boundary_faces(const cfd_mesh_view& m) {
+  std::vector<BndFace> out;
+  for (uint32_t i = 0; i < m.num_cells; ++i)
+    for (uint32_t k = m.cell_face_offsets[i]; k < m.cell_face_offsets[i + 1]; ++k) {
+      const uint32_t f = m.cell_faces[k];
+      const uint32_t bt = m.face_boundary[f] & 3u;
+      if (m.face_neighbor[f] == UINT32_MAX && (bt == 1u || bt == 3u))
+        out.push_back({f, i, k - m.cell_face_offsets[i], bt, m.face_nx[f], m.face_ny[f], m.face_cx[f], m.face_cy[f]});
+    }
+  std::sort(out.begin(), out.end(), [](const BndFace& a, const BndFace& b) { return a.face < b.face; });
+  return out;
+}
+
 }  // namespace cfd2

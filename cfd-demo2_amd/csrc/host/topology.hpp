@@ -74,4 +74,25 @@ struct WallFace {
 // in the closed box; none for an inverted box (x1 < x0)
 std::vector<uint32_t> wall_faces_in_box(const std::vector<WallFace>& wall, double x0, double y0, double x1, double y1);
 
+// The force region (Solver::set_force_region): the wall faces the force sums,
+// the wall-motion sums and the monitor's records run over.
+struct ForceRegion {
+  bool on = false;               // some face selected: every rank runs the same kernel form
+  uint32_t faces = 0;            // selected wall faces, whole mesh
+  uint64_t gen = 0;              // set_force_region calls
+  double box[4] = {0, 0, -1, 0};
+  uint16_t* mask = nullptr;      // [N] selected wall slots, in the solver's arena (first non-empty region)
+  bool holds(double cx, double cy) const { return cx >= box[0] && cx <= box[2] && cy >= box[1] && cy <= box[3]; }
+};
+
+// every inlet and wall face of the mesh, ascending face index (boundary_velocity.hpp)
+struct BndFace {
+  uint32_t face;
+  uint32_t cell, slot;
+  uint32_t btype;     // 1 inlet, 3 wall
+  double nx, ny;      // the f64 face normal (its sign does not matter here)
+  double cx, cy;      // the f64 face centre
+};
+std::vector<BndFace> boundary_faces(const cfd_mesh_view& m);  // after build_topology checked the mesh
+
 }  // namespace cfd2
