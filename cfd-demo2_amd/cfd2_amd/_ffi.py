@@ -247,6 +247,17 @@ class BoundaryVelocity(C.Structure):  # cfd_boundary_velocity
                 ("max_normal_removed", C.c_double)]
 
 
+class ViscosityModel(C.Structure):  # cfd_viscosity_model
+    _fields_ = [("kind", C.c_int32), ("K", C.c_float), ("n", C.c_float), ("gamma_min", C.c_float),
+                ("mu0", C.c_float), ("mu_inf", C.c_float), ("lam", C.c_float), ("mu_min", C.c_float),
+                ("mu_max", C.c_float)]
+
+
+class ViscosityStats(C.Structure):  # cfd_viscosity_stats
+    _fields_ = [("mu_min", C.c_float), ("mu_max", C.c_float), ("clamped_below", C.c_uint32),
+                ("clamped_above", C.c_uint32)]
+
+
 class WallMotion(C.Structure):  # cfd_wall_motion
     _fields_ = [("torque_pressure", C.c_double), ("torque_viscous", C.c_double), ("power", C.c_double),
                 ("region_faces", C.c_uint32), ("moving_faces", C.c_uint32)]
@@ -401,6 +412,8 @@ EXPORTED = [
     "cfd_set_scalar_buoyancy", "cfd_set_gravity", "cfd_buoyancy_get", "cfd_buoyancy_force_get",
     "cfd_set_boundary_velocity", "cfd_set_boundary_velocity_scale", "cfd_boundary_velocity_get",
     "cfd_wall_motion_get",
+    "cfd_set_viscosity_field", "cfd_get_viscosity_field", "cfd_set_viscosity_model", "cfd_viscosity_evaluate",
+    "cfd_get_shear_rate", "cfd_viscosity_stats_get", "cfd_debug_pow_det",
     "cfd_particles_set_mesh", "cfd_particle_config_default", "cfd_particles_enable", "cfd_particles_seed",
     "cfd_particles_advance", "cfd_particles_get", "cfd_particles_stats_get", "cfd_render_particles",
     "cfd_tstats_enable", "cfd_tstats_disable", "cfd_tstats_reset", "cfd_tstats_accumulate", "cfd_tstats_info",

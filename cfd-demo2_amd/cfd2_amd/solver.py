@@ -148,6 +148,14 @@ def _bind():
     L.cfd_set_boundary_velocity_scale.argtypes = [_vp, C.c_float, C.c_float]
     L.cfd_boundary_velocity_get.argtypes = [_vp, C.POINTER(_ffi.BoundaryVelocity)]
     L.cfd_wall_motion_get.argtypes = [_vp, C.c_double, C.c_double, C.POINTER(_ffi.WallMotion)]
+    L.cfd_set_viscosity_field.argtypes = [_vp, fp, C.c_uint32]
+    L.cfd_get_viscosity_field.argtypes = [_vp, fp]
+    L.cfd_set_viscosity_model.argtypes = [_vp, C.POINTER(_ffi.ViscosityModel)]
+    L.cfd_viscosity_evaluate.argtypes = [_vp]
+    L.cfd_get_shear_rate.argtypes = [_vp, fp]
+    L.cfd_viscosity_stats_get.argtypes = [_vp, C.POINTER(_ffi.ViscosityStats)]
+    dp_ = C.POINTER(C.c_double)
+    L.cfd_debug_pow_det.argtypes = [dp_, dp_, dp_, C.c_uint32]
     L.cfd_render_set_polygons.argtypes = [_vp, C.c_uint32, dp, dp, u32p, u32p]
     L.cfd_render_set_view.argtypes = [_vp, C.c_int32, C.c_int32, dp, u32p]
     L.cfd_render.argtypes = [_vp, C.c_int32, C.c_int32, fp, u8p, fp]
@@ -639,6 +647,62 @@ class GpuSolver:
         self._call("cfd_wall_motion_get", float(x0), float(y0), C.byref(w))
         return WallMotion(float(w.torque_pressure), float(w.torque_viscous), float(w.power), int(w.region_faces),
                           int(w.moving_faces))
+
+    # -- variable viscosity: a viscosity per cell -----------------------------------
+    def set_viscosity_field(self, mu) -> None:
+        """cfd_set_viscosity_field: ``mu`` [num_cells], every value finite and
+        > 0, rounded to float32: the viscosity of each cell, in place of the one
+        of set_viscosity().  A face between two cells takes the arithmetic mean,
+        a boundary face its cell's value.  Enables the field or replaces its
+        values (one upload; nothing is re-captured); takes effect at the next
+        step().  Not stored in a checkpoint.  One GPU only."""
+        m = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1).astype(np.float32))
+        if len(m) == 0:
+            raise ValueError("an empty viscosity field: clear_viscosity_field() clears it")
+        self._call("cfd_set_viscosity_field", m.ctypes.data_as(C.POINTER(C.c_float)), len(m))
+
+    def clear_viscosity_field(self) -> None:
+        """The next step() runs the plain kernels again, with set_viscosity()'s value."""
+        self._call("cfd_set_viscosity_field", None, 0)
+
+    def viscosity_field(self) -> np.ndarray:
+        """cfd_get_viscosity_field: the float32 field the next step() will read.
+        Raises when none is set."""
+        out = np.empty(self.num_cells, dtype=np.float32)
+        self._call("cfd_get_viscosity_field", out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
+
+    VISCOSITY_KINDS = {"none": 0, "power_law": 1, "carreau": 2}
+
+    def set_viscosity_model(self, kind, K=0.0, n=1.0, gamma_min=0.0, mu0=0.0, mu_inf=0.0, lam=0.0, mu_min=0.0,
+                            mu_max=0.0) -> None:
+        """cfd_set_viscosity_model: ``"power_law"`` (mu = K max(gdot, gamma_min)^(n-1))
+        or ``"carreau"`` (mu = mu_inf + (mu0 - mu_inf) (1 + (lam gdot)^2)^((n-1)/2)),
+        clamped to [mu_min, mu_max]; evaluated on the device at the start of
+        every step() from the velocity the step starts from.  ``"none"`` stops
+        the evaluation and leaves the field.  Not stored in a checkpoint."""
+        k = self.VISCOSITY_KINDS[kind] if isinstance(kind, str) else int(kind)
+        m = _ffi.ViscosityModel(k, float(K), float(n), float(gamma_min), float(mu0), float(mu_inf), float(lam),
+                                float(mu_min), float(mu_max))
+        self._call("cfd_set_viscosity_model", C.byref(m))
+
+    def viscosity_evaluate(self) -> None:
+        """cfd_viscosity_evaluate: the model on the current state, now."""
+        self._call("cfd_viscosity_evaluate")
+
+    def shear_rate(self) -> np.ndarray:
+        """cfd_get_shear_rate: the float32 shear rate of the last evaluation."""
+        out = np.empty(self.num_cells, dtype=np.float32)
+        self._call("cfd_get_shear_rate", out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
+
+    def viscosity_stats(self) -> dict:
+        """cfd_viscosity_stats_get: min and max of the field and the cells clamped
+        below and above, of the last evaluation."""
+        st = _ffi.ViscosityStats()
+        self._call("cfd_viscosity_stats_get", C.byref(st))
+        return dict(mu_min=float(st.mu_min), mu_max=float(st.mu_max), clamped_below=int(st.clamped_below),
+                    clamped_above=int(st.clamped_above))
 
     # -- frames on the device: a cell field as an RGBA8 image ---------------------
     def set_render_mesh(self, mesh) -> None:

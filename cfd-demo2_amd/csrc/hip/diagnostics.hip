@@ -25,8 +25,12 @@ namespace {
 // BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs): the
 // face value follows prepare_cell<true>, the viscous force of a selected wall
 // slot takes u - ub.
-template <bool FIELDS, bool FORCE, bool BCV>
-__device__ __forceinline__ void flow_diag_block(const FlowDiagArgs& a, const BcvArgs& v) {
+// VISC: the form with a viscosity per cell: the viscous force of a wall slot
+// takes mu[i] for c.viscosity (one more coalesced 4-byte load per cell).  Only
+// the FORCE instances have it: nothing else here reads the viscosity.
+template <bool FIELDS, bool FORCE, bool BCV, bool VISC = false>
+__device__ __forceinline__ void flow_diag_block(const FlowDiagArgs& a, const BcvArgs& v,
+                                                const float* __restrict__ mu = nullptr) {
   __shared__ double lsum[kFlowDiagSums][4][4];  // [sum][chunk q][quarter w]
   __shared__ unsigned long long lmax[3][4];
   const uint32_t N = a.N;
@@ -46,6 +50,8 @@ __device__ __forceinline__ void flow_diag_block(const FlowDiagArgs& a, const Bcv
       mask = a.wall_mask[i];
       pc = a.p[i];
     }
+    float visc = c.viscosity;
+    if constexpr (VISC) visc = mu[i];
     const uint32_t nf = fs.nface[i];
     uint32_t brow = 0;
     if constexpr (BCV) brow = v.sel[i];
@@ -118,8 +124,8 @@ __device__ __forceinline__ void flow_diag_block(const FlowDiagArgs& a, const Bcv
               ruy = (double)uc.y - (double)sby;
             }
           }
-          fvx += (double)c.viscosity * rux * ad / dist;
-          fvy += (double)c.viscosity * ruy * ad / dist;
+          fvx += (double)visc * rux * ad / dist;
+          fvy += (double)visc * ruy * ad / dist;
         }
       }
     }
@@ -170,6 +176,14 @@ template <bool FIELDS, bool FORCE>
 __global__ void __launch_bounds__(kBlock) k_flow_diag_bcv(FlowDiagArgs a, BcvArgs v) {
   flow_diag_block<FIELDS, FORCE, true>(a, v);
 }
+template <bool FIELDS>
+__global__ void __launch_bounds__(kBlock) k_flow_diag_visc(FlowDiagArgs a, const float* __restrict__ mu) {
+  flow_diag_block<FIELDS, true, false, true>(a, BcvArgs{}, mu);
+}
+template <bool FIELDS>
+__global__ void __launch_bounds__(kBlock) k_flow_diag_bcv_visc(FlowDiagArgs a, BcvArgs v, const float* __restrict__ mu) {
+  flow_diag_block<FIELDS, true, true, true>(a, v, mu);
+}
 
 // The wall-motion sums (kernels.hpp WallMotionArgs) over the shared skeleton:
 // a cell with a force-region slot walks the set bits of its mask in ascending
@@ -187,6 +201,7 @@ __global__ void __launch_bounds__(kBlock) k_wall_motion(WallMotionArgs a) {
       const float pc = a.p[i];
       const uint32_t crow = a.crow[i];  // != 0: the host gives every cell of the region a row
       const uint32_t brow = a.v.sel ? a.v.sel[i] : 0u;
+      const float visc = a.mu ? a.mu[i] : c.viscosity;  // a viscosity per cell, as k_flow_diag's VISC form
       while (walls && crow) {
         const uint32_t k = (uint32_t)__ffs((int)walls) - 1u;
         walls &= walls - 1u;
@@ -211,8 +226,8 @@ __global__ void __launch_bounds__(kBlock) k_wall_motion(WallMotionArgs a) {
           rux = (double)uc.x - (double)sbx;
           ruy = (double)uc.y - (double)sby;
         }
-        const double fvx = (double)c.viscosity * rux * ad / dist;
-        const double fvy = (double)c.viscosity * ruy * ad / dist;
+        const double fvx = (double)visc * rux * ad / dist;
+        const double fvy = (double)visc * ruy * ad / dist;
         const double2 fc = a.ctr[(size_t)(crow - 1u) * (uint32_t)fs.wf + k];
         const double rx = fc.x - a.x0, ry = fc.y - a.y0;
         t[0] += rx * fpy - ry * fpx;
@@ -227,7 +242,8 @@ __global__ void __launch_bounds__(kBlock) k_wall_motion(WallMotionArgs a) {
 
 }  // namespace
 
-void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, unsigned long long* maxout, hipStream_t s) {
+void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, const float* mu, unsigned long long* maxout,
+                      hipStream_t s) {
   const uint32_t nb = red_blocks(a.N);
   if (nb) {
     const bool fields = a.omega_out != nullptr, force = a.wall_mask != nullptr;
@@ -238,7 +254,17 @@ void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, unsigned long lon
       else
         hipLaunchKernelGGL(plain, g, b, 0, s, a);
     };
-    if (fields && force)
+    auto go_visc = [&](auto plain, auto bcv) {  // the pair of one FIELDS, with a force region
+      if (v)
+        hipLaunchKernelGGL(bcv, g, b, 0, s, a, *v, mu);
+      else
+        hipLaunchKernelGGL(plain, g, b, 0, s, a, mu);
+    };
+    if (mu && force && fields)
+      go_visc(k_flow_diag_visc<true>, k_flow_diag_bcv_visc<true>);
+    else if (mu && force)
+      go_visc(k_flow_diag_visc<false>, k_flow_diag_bcv_visc<false>);
+    else if (fields && force)
       go(k_flow_diag<true, true>, k_flow_diag_bcv<true, true>);
     else if (fields)
       go(k_flow_diag<true, false>, k_flow_diag_bcv<true, false>);

@@ -17,9 +17,14 @@ namespace {
 // BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs): one
 // more coalesced 4-byte load per cell, the table only inside a boundary slot's
 // branch of a cell that has a row; everything else is the plain form's.
-template <bool BCV>
-__device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs& v, uint32_t i, float& dp_new,
-                                             float2& gp_new, float2& gu_new, float2& gv_new) {
+// VISC: the form with a viscosity per cell (kernels.hpp "variable viscosity"):
+// one more coalesced 4-byte load per cell and one 4-byte gather per interior
+// slot, beside the u[other] gathers; the face viscosity stands where
+// c.viscosity stood and nothing else changes.
+template <bool BCV, bool VISC>
+__device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs& v, const float* __restrict__ mu,
+                                             uint32_t i, float& dp_new, float2& gp_new, float2& gu_new,
+                                             float2& gv_new) {
   const uint32_t N = a.N;
   const cfd_constants c = a.c;
   const FaceSlots fs = a.fs;
@@ -39,12 +44,16 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs
   const uint32_t nf = fs.nface[i];
   uint32_t brow = 0;
   if constexpr (BCV) brow = v.sel[i];
+  float mui = 0.0f;
+  if constexpr (VISC) mui = mu[i];
   for (uint32_t k = 0; k < nf; ++k) {
     const size_t e = (size_t)k * N + i;
     const uint32_t meta = fs.meta[e];
     const int32_t other = fs.other[e];
     const uint32_t bt = meta & kMetaBtypeMask;
     const bool own = (meta & kMetaOwner) != 0;
+    float mu_f = c.viscosity;  // VISC: the face viscosity, mu[i] on a boundary slot
+    if constexpr (VISC) mu_f = mui;
     bool bsel = false;  // BCV: a selected slot, its velocity (sbx, sby)
     float sbx = 0.0f, sby = 0.0f;
     if constexpr (BCV) {
@@ -73,6 +82,7 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs
       const float p_oth = a.st.p[other];
       const float dp_oth = a.st.dp[other];
       const float2 gp_oth = a.st.gp[other];
+      if constexpr (VISC) mu_f = 0.5f * (mui + mu[other]);
       uo = u_oth;
       po_other = p_oth;
       const float2 uow = own ? uc : u_oth, ung = own ? u_oth : uc;
@@ -108,7 +118,7 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs
     }
     const float flux_out = own ? flux : -flux;
     a.flux_s[e] = flux_out;
-    const float diff_coeff = c.viscosity * area / fs.dist_e[e];
+    const float diff_coeff = mu_f * area / fs.dist_e[e];
     const float conv_diag = flux_out > 0.0f ? flux_out : 0.0f;
     if (other != kNoCell) {
       diag_coeff += diff_coeff + conv_diag;
@@ -166,7 +176,7 @@ __global__ void __launch_bounds__(kBlock) k_prepare(PrepareArgs a) {
   if (i >= a.N) return;
   float dp;
   float2 gp, gu, gv;
-  prepare_cell<false>(a, BcvArgs{}, i, dp, gp, gu, gv);
+  prepare_cell<false, false>(a, BcvArgs{}, nullptr, i, dp, gp, gu, gv);
   a.dp_out[i] = dp;
   a.gp_out[i] = gp;
   a.grad_u[i] = gu;
@@ -177,7 +187,29 @@ __global__ void __launch_bounds__(kBlock) k_prepare_bcv(PrepareArgs a, BcvArgs v
   if (i >= a.N) return;
   float dp;
   float2 gp, gu, gv;
-  prepare_cell<true>(a, v, i, dp, gp, gu, gv);
+  prepare_cell<true, false>(a, v, nullptr, i, dp, gp, gu, gv);
+  a.dp_out[i] = dp;
+  a.gp_out[i] = gp;
+  a.grad_u[i] = gu;
+  a.grad_v[i] = gv;
+}
+__global__ void __launch_bounds__(kBlock) k_prepare_visc(PrepareArgs a, const float* __restrict__ mu) {
+  const uint32_t i = row_id();
+  if (i >= a.N) return;
+  float dp;
+  float2 gp, gu, gv;
+  prepare_cell<false, true>(a, BcvArgs{}, mu, i, dp, gp, gu, gv);
+  a.dp_out[i] = dp;
+  a.gp_out[i] = gp;
+  a.grad_u[i] = gu;
+  a.grad_v[i] = gv;
+}
+__global__ void __launch_bounds__(kBlock) k_prepare_bcv_visc(PrepareArgs a, BcvArgs v, const float* __restrict__ mu) {
+  const uint32_t i = row_id();
+  if (i >= a.N) return;
+  float dp;
+  float2 gp, gu, gv;
+  prepare_cell<true, true>(a, v, mu, i, dp, gp, gu, gv);
   a.dp_out[i] = dp;
   a.gp_out[i] = gp;
   a.grad_u[i] = gu;
@@ -193,7 +225,7 @@ __global__ void __launch_bounds__(64) k_prepare_ordered(PrepareArgs a) {
     const uint32_t i = b0 + threadIdx.x;
     float dp = 0.0f;
     float2 gp = make_float2(0.0f, 0.0f), gu = gp, gv = gp;
-    if (i < a.N) prepare_cell<false>(a, BcvArgs{}, i, dp, gp, gu, gv);
+    if (i < a.N) prepare_cell<false, false>(a, BcvArgs{}, nullptr, i, dp, gp, gu, gv);
     __syncthreads();  // the workgroup's reads complete
     if (i < a.N) {
       a.dp_out[i] = dp;
@@ -221,8 +253,11 @@ __global__ void __launch_bounds__(kBlock) k_flux_mirror(float* flux_s, const int
 // branch's loads differently, and k_assemble is to stay the code it was.
 // BCV: the form with prescribed boundary velocities (kernels.hpp BcvArgs), as in
 // prepare_cell: nothing is added to an interior slot.
-template <bool BUOY, bool BCV>
-__device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b, const BcvArgs v) {
+// VISC: the form with a viscosity per cell, as in prepare_cell, with this
+// kernel's own distance (dist_a); the gather sits beside dp[other].
+template <bool BUOY, bool BCV, bool VISC>
+__device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b, const BcvArgs v,
+                                              const float* __restrict__ mu) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
@@ -253,6 +288,8 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
   const uint32_t nf = fs.nface[i];
   uint32_t brow = 0;
   if constexpr (BCV) brow = v.sel[i];
+  float mui = 0.0f;
+  if constexpr (VISC) mui = mu[i];
   for (uint32_t k = 0; k < nf; ++k) {
     const size_t e = (size_t)k * N + i;
     const uint32_t meta = fs.meta[e];
@@ -262,7 +299,9 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
     const float nx = fs.nx[e], ny = fs.ny[e];
     const float flux = a.flux_s[e];
     const float dist = fs.dist_a[e];
-    const float diff_coeff = c.viscosity * area / dist;
+    float mu_f = c.viscosity;  // VISC: the face viscosity, mu[i] on a boundary slot
+    if constexpr (VISC) mu_f = other != kNoCell ? 0.5f * (mui + mu[other]) : mui;
+    const float diff_coeff = mu_f * area / dist;
     const float conv_diag = flux > 0.0f ? flux : 0.0f;
     const float conv_off = flux > 0.0f ? 0.0f : flux;
     if (other != kNoCell) {
@@ -399,16 +438,30 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
   a.dinv_p[i] = safe_inverse(sdiag);
 }
 __global__ void __launch_bounds__(kBlock) k_assemble(AssembleArgs a) {
-  assemble_cell<false, false>(a, BuoyancyArgs{}, BcvArgs{});
+  assemble_cell<false, false, false>(a, BuoyancyArgs{}, BcvArgs{}, nullptr);
 }
 __global__ void __launch_bounds__(kBlock) k_assemble_buoyant(AssembleArgs a, BuoyancyArgs b) {
-  assemble_cell<true, false>(a, b, BcvArgs{});
+  assemble_cell<true, false, false>(a, b, BcvArgs{}, nullptr);
 }
 __global__ void __launch_bounds__(kBlock) k_assemble_bcv(AssembleArgs a, BcvArgs v) {
-  assemble_cell<false, true>(a, BuoyancyArgs{}, v);
+  assemble_cell<false, true, false>(a, BuoyancyArgs{}, v, nullptr);
 }
 __global__ void __launch_bounds__(kBlock) k_assemble_buoyant_bcv(AssembleArgs a, BuoyancyArgs b, BcvArgs v) {
-  assemble_cell<true, true>(a, b, v);
+  assemble_cell<true, true, false>(a, b, v, nullptr);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_visc(AssembleArgs a, const float* __restrict__ mu) {
+  assemble_cell<false, false, true>(a, BuoyancyArgs{}, BcvArgs{}, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_buoyant_visc(AssembleArgs a, BuoyancyArgs b,
+                                                                  const float* __restrict__ mu) {
+  assemble_cell<true, false, true>(a, b, BcvArgs{}, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_bcv_visc(AssembleArgs a, BcvArgs v, const float* __restrict__ mu) {
+  assemble_cell<false, true, true>(a, BuoyancyArgs{}, v, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_assemble_buoyant_bcv_visc(AssembleArgs a, BuoyancyArgs b, BcvArgs v,
+                                                                      const float* __restrict__ mu) {
+  assemble_cell<true, true, true>(a, b, v, mu);
 }
 
 // update_fields_from_coupled.wgsl:45-98.  The reference folds max|du|, max|dp|
@@ -506,6 +559,26 @@ void launch_assemble_bcv(const AssembleArgs& a, const BuoyancyArgs* buoy, const 
     hipLaunchKernelGGL(k_assemble_buoyant_bcv, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, *buoy, v);
   else
     hipLaunchKernelGGL(k_assemble_bcv, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, v);
+}
+void launch_prepare_visc(const PrepareArgs& a, const BcvArgs* v, const float* mu, hipStream_t s) {
+  if (!a.N) return;
+  if (v)
+    hipLaunchKernelGGL(k_prepare_bcv_visc, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, *v, mu);
+  else
+    hipLaunchKernelGGL(k_prepare_visc, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, mu);
+}
+void launch_assemble_visc(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs* v, const float* mu,
+                          hipStream_t s) {
+  if (!a.N) return;
+  const dim3 g(grid_for(a.N)), b(kBlock);
+  if (buoy && v)
+    hipLaunchKernelGGL(k_assemble_buoyant_bcv_visc, g, b, 0, s, a, *buoy, *v, mu);
+  else if (v)
+    hipLaunchKernelGGL(k_assemble_bcv_visc, g, b, 0, s, a, *v, mu);
+  else if (buoy)
+    hipLaunchKernelGGL(k_assemble_buoyant_visc, g, b, 0, s, a, *buoy, mu);
+  else
+    hipLaunchKernelGGL(k_assemble_visc, g, b, 0, s, a, mu);
 }
 void launch_update_fields(uint32_t N, float au, float ap, const float* x, float2* u, float* p,
                           uint32_t* blockmax, uint32_t* maxbits, uint32_t* host_out, hipStream_t s) {

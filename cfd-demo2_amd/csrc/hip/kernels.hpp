@@ -381,6 +381,38 @@ constexpr float kBcvInlet = 1.0f, kBcvWall = 3.0f;
 void launch_prepare_bcv(const PrepareArgs& a, const BcvArgs& v, hipStream_t s);
 // buoy: null for the form without the Boussinesq source
 void launch_assemble_bcv(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs& v, hipStream_t s);
+// Variable viscosity (include/cfd2_amd.h "Arithmetic of variable viscosity" is
+// the contract), one more kernel argument of the VISC forms only: mu [N], the
+// viscosity per cell as it stands at the launch.  Per face slot of cell i, one
+// f32 rounding per operation,
+//   interior  mu_f = 0.5f * (mu[i] + mu[other])   (the same bits from either side)
+//   boundary  mu_f = mu[i]
+// and mu_f stands where c.viscosity stood: diff_coeff = mu_f * area / dist with
+// the kernel's own distance (dist_e in prepare, dist_a in assemble).  One more
+// coalesced 4-byte load per cell and one 4-byte gather per interior slot.
+// v / buoy: null for the forms without them.
+void launch_prepare_visc(const PrepareArgs& a, const BcvArgs* v, const float* mu, hipStream_t s);
+void launch_assemble_visc(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs* v, const float* mu,
+                          hipStream_t s);
+// ---- viscosity.hip ----
+// The viscosity models (include/cfd2_amd.h "Arithmetic of the viscosity
+// models"): per cell the Green-Gauss gradients of u as prepare_cell forms them,
+// the f32 shear rate, the model in f64 (pow_det.hpp), clamped, into mu and
+// gdot.  stats[0..3]: min and max of mu as bit patterns, the cells clamped
+// below and above; the caller sets them to {0xFFFFFFFF, 0, 0, 0} before the
+// launch.  v != null: the face values of the BCV form.
+struct ViscosityModelArgs {
+  uint32_t N;
+  cfd_constants c;
+  FaceSlots fs;
+  const float* vol;
+  const float2* u;
+  cfd_viscosity_model model;
+  float* mu;        // [N] out
+  float* gdot;      // [N] out
+  uint32_t* stats;  // [4]
+};
+void launch_viscosity_model(const ViscosityModelArgs& a, const BcvArgs* v, hipStream_t s);
 // writes per-block max bit patterns to blockmax[2*nb] and the final pair to maxbits[0..1]
 // (and to host_out[0..1], a device view of pinned host memory, when non-null)
 void launch_update_fields(uint32_t N, float alpha_u, float alpha_p, const float* x, float2* u,
@@ -573,7 +605,9 @@ struct FlowDiagArgs {
 // v != null, the BCV form (BcvArgs above): the face value of a selected inlet or
 // wall slot is (ubx, uby), and the viscous force of a selected wall slot in the
 // force region is viscosity * ((double)u - (double)ubx) * area / dist_e.
-void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, unsigned long long* maxout, hipStream_t s);
+// mu != null, the VISC form: (double)mu[i] for the viscosity of cell i's wall slots.
+void launch_flow_diag(const FlowDiagArgs& a, const BcvArgs* v, const float* mu, unsigned long long* maxout,
+                      hipStream_t s);
 // Read-only wall-motion sums over the force-region wall slots (wall_mask, as
 // FlowDiagArgs): per cell, in f64, in ascending slot order, with F_p = p n area
 // and F_v = viscosity (u - ub) area / dist_e as k_flow_diag forms them and the
@@ -594,6 +628,7 @@ struct WallMotionArgs {
   const uint32_t* crow;       // [N]
   const double2* ctr;         // [rows * fs.wf]
   BcvArgs v;
+  const float* mu;            // [N] the viscosity per cell, or null: c.viscosity
   double x0, y0;
   SumOut out;                 // [kWallMotionSums * np]
 };
@@ -969,9 +1004,9 @@ struct SurfaceArgs {
   double w, r;            // accumulate: the sample's weight and w / (W + w), from the host
 };
 // v null: the plain form
-void launch_surface_sample(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s);
+void launch_surface_sample(const SurfaceArgs& a, const BcvArgs* v, const float* mu, hipStream_t s);
 // the same evaluation, every channel into its mean and M2 (mean_update /
 // m2_update of device_util.hpp) instead of a.out: one launch per sample
-void launch_surface_accumulate(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s);
+void launch_surface_accumulate(const SurfaceArgs& a, const BcvArgs* v, const float* mu, hipStream_t s);
 
 }  // namespace cfd2

@@ -29,12 +29,17 @@ namespace cfd2 {
 namespace {
 
 // Face j of the table: emit(channel, value) for every channel in ascending order.
-template <bool BCV, class Emit>
-__device__ __forceinline__ void surface_face(const SurfaceArgs& a, const BcvArgs& v, uint32_t j, Emit&& emit) {
+// VISC: the form with a viscosity per cell (one more gather, mu[i], with the
+// others): channels 3 and 4 take it for c.viscosity, as k_flow_diag's VISC form.
+template <bool BCV, bool VISC, class Emit>
+__device__ __forceinline__ void surface_face(const SurfaceArgs& a, const BcvArgs& v, const float* __restrict__ mu,
+                                             uint32_t j, Emit&& emit) {
   const uint32_t i = a.cell[j], k = a.slot[j];
   const size_t e = (size_t)k * a.N + i;
   const float pc = a.p[i];
   const float2 uc = a.u[i];
+  float visc = a.c.viscosity;
+  if constexpr (VISC) visc = mu[i];
   const float area = a.area[e], nx = a.nx[e], ny = a.ny[e], de = a.dist_e[e];
   float ph[kTimeStatsMaxFields];
   uint32_t sw[kTimeStatsMaxFields];
@@ -72,8 +77,8 @@ __device__ __forceinline__ void surface_face(const SurfaceArgs& a, const BcvArgs
       ruy = (double)uc.y - (double)sby;
     }
   }
-  emit(3u, (double)a.c.viscosity * rux * ad / dist);
-  emit(4u, (double)a.c.viscosity * ruy * ad / dist);
+  emit(3u, (double)visc * rux * ad / dist);
+  emit(4u, (double)visc * ruy * ad / dist);
 #pragma unroll
   for (uint32_t f = 0; f < kTimeStatsMaxFields; ++f) {
     if (f >= a.nf) break;  // uniform
@@ -90,24 +95,26 @@ __device__ __forceinline__ void surface_face(const SurfaceArgs& a, const BcvArgs
   }
 }
 
-template <bool BCV>
-__device__ __forceinline__ void surface_sample(const SurfaceArgs& a, const BcvArgs& v) {
+template <bool BCV, bool VISC = false>
+__device__ __forceinline__ void surface_sample(const SurfaceArgs& a, const BcvArgs& v,
+                                               const float* __restrict__ mu = nullptr) {
   const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
   if (j >= a.n) return;
   double* out = a.out + j;
   const size_t ld = a.ld;
-  surface_face<BCV>(a, v, j, [&](uint32_t ch, double x) { out[(size_t)ch * ld] = x; });
+  surface_face<BCV, VISC>(a, v, mu, j, [&](uint32_t ch, double x) { out[(size_t)ch * ld] = x; });
 }
 
-template <bool BCV>
-__device__ __forceinline__ void surface_accumulate(const SurfaceArgs& a, const BcvArgs& v) {
+template <bool BCV, bool VISC = false>
+__device__ __forceinline__ void surface_accumulate(const SurfaceArgs& a, const BcvArgs& v,
+                                                   const float* __restrict__ mu = nullptr) {
   const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
   if (j >= a.n) return;
   double* mean = a.mean + j;
   double* m2 = a.m2 + j;
   const size_t ld = a.ld;
   const double w = a.w, r = a.r;
-  surface_face<BCV>(a, v, j, [&](uint32_t ch, double x) {
+  surface_face<BCV, VISC>(a, v, mu, j, [&](uint32_t ch, double x) {
     const size_t o = (size_t)ch * ld;
     double m = mean[o], M = m2[o];
     const Dev q = mean_update(x, r, m);
@@ -125,22 +132,44 @@ __global__ void __launch_bounds__(kBlock) k_surface_accumulate(SurfaceArgs a) {
 __global__ void __launch_bounds__(kBlock) k_surface_accumulate_bcv(SurfaceArgs a, BcvArgs v) {
   surface_accumulate<true>(a, v);
 }
+__global__ void __launch_bounds__(kBlock) k_surface_sample_visc(SurfaceArgs a, const float* __restrict__ mu) {
+  surface_sample<false, true>(a, BcvArgs{}, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_surface_sample_bcv_visc(SurfaceArgs a, BcvArgs v,
+                                                                    const float* __restrict__ mu) {
+  surface_sample<true, true>(a, v, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_surface_accumulate_visc(SurfaceArgs a, const float* __restrict__ mu) {
+  surface_accumulate<false, true>(a, BcvArgs{}, mu);
+}
+__global__ void __launch_bounds__(kBlock) k_surface_accumulate_bcv_visc(SurfaceArgs a, BcvArgs v,
+                                                                        const float* __restrict__ mu) {
+  surface_accumulate<true, true>(a, v, mu);
+}
 
 }  // namespace
 
-void launch_surface_sample(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s) {
+void launch_surface_sample(const SurfaceArgs& a, const BcvArgs* v, const float* mu, hipStream_t s) {
   if (a.n == 0) return;
   const dim3 g(grid_for(a.n)), b(kBlock);
-  if (v)
+  if (mu && v)
+    hipLaunchKernelGGL(k_surface_sample_bcv_visc, g, b, 0, s, a, *v, mu);
+  else if (mu)
+    hipLaunchKernelGGL(k_surface_sample_visc, g, b, 0, s, a, mu);
+  else if (v)
     hipLaunchKernelGGL(k_surface_sample_bcv, g, b, 0, s, a, *v);
   else
     hipLaunchKernelGGL(k_surface_sample, g, b, 0, s, a);
 }
 
-void launch_surface_accumulate(const SurfaceArgs& a, const BcvArgs* v, hipStream_t s) {
+void launch_surface_accumulate(const SurfaceArgs& a, const BcvArgs* v, const float* mu, hipStream_t s) {
   if (a.n == 0) return;
   const dim3 g(grid_for(a.n)), b(kBlock);
-  if (v)
+  if (mu && v)
+    hipLaunchKernelGGL(k_surface_accumulate_bcv_visc, g, b, 0, s, a, *v, mu);
+  else if (mu)
+    hipLaunchKernelGGL(k_surface_accumulate_visc, g, b, 0, s, a, mu);
+  else if (v)
     hipLaunchKernelGGL(k_surface_accumulate_bcv, g, b, 0, s, a, *v);
   else
     hipLaunchKernelGGL(k_surface_accumulate, g, b, 0, s, a);

@@ -155,6 +155,7 @@ void BoundaryVelocity::wall_motion(const FlowView& flow, const ForceRegion& regi
   a.crow = wm_crow;
   a.ctr = wm_ctr;
   a.v = on() ? args() : BcvArgs{nullptr, nullptr, scale[0], scale[1]};
+  a.mu = flow.visc_mu;
   a.x0 = x0;
   a.y0 = y0;
   a.out = flow.sums.buf(wm_sums, kWallMotionSums, wm_arena);

@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "../hip/pow_det.hpp"
 #include "error.hpp"
 #include "solver_impl.hpp"
 
@@ -693,6 +694,53 @@ cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_mot
     S.bcv_need("wall motion");
     S.bcv.wall_motion(S.view(nullptr), S.region, S.wall_faces, x0, y0, out);
   });
+}
+
+// ------------------------------------------------------- variable viscosity
+cfd_status cfd_set_viscosity_field(cfd_solver* s, const float* mu, uint32_t n) {
+  CHECK_S(s);
+  if (n && !mu) return set_error(CFD_ERR_INVALID, "null mu");
+  return guard([&] {
+    s->s->visc_need("viscosity field");
+    s->s->visc.set(s->s->view(nullptr), mu, n);
+  });
+}
+cfd_status cfd_get_viscosity_field(cfd_solver* s, float* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->visc.get(s->s->view(nullptr), out); });
+}
+
+cfd_status cfd_set_viscosity_model(cfd_solver* s, const cfd_viscosity_model* model) {
+  CHECK_S(s);
+  if (!model) return set_error(CFD_ERR_INVALID, "null model");
+  return guard([&] {
+    s->s->visc_need("viscosity model");
+    s->s->visc.set_model(s->s->view(nullptr), *model);
+  });
+}
+cfd_status cfd_viscosity_evaluate(cfd_solver* s) {
+  CHECK_S(s);
+  return guard([&] {
+    const cfd2::FlowView flow = s->s->view(nullptr);
+    s->s->visc.evaluate(flow);
+    flow.sync();
+  });
+}
+cfd_status cfd_get_shear_rate(cfd_solver* s, float* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->visc.shear_rate(s->s->view(nullptr), out); });
+}
+cfd_status cfd_viscosity_stats_get(cfd_solver* s, cfd_viscosity_stats* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] { s->s->visc.stats_get(s->s->view(nullptr), out); });
+}
+cfd_status cfd_debug_pow_det(const double* x, const double* y, double* out, uint32_t n) {
+  if (n && (!x || !y || !out)) return set_error(CFD_ERR_INVALID, "null x / y / out");
+  for (uint32_t i = 0; i < n; ++i) out[i] = cfd2::pow_det(x[i], y[i]);
+  return CFD_OK;
 }
 
 // ------------------------------------------------------- frames on the device

@@ -16,6 +16,9 @@ void Solver::set_reference_semantics(int flags) {
   if ((flags & 2) && bcv.on())
     throw std::invalid_argument("reference semantics: the racy prepare has no form with prescribed boundary velocities "
                                 "(clear them first)");
+  if ((flags & (1 | 2)) && visc.on())
+    throw std::invalid_argument("reference semantics: the racy prepare and the in-place smoother have no form with a "
+                                "viscosity field (clear it first)");
   if ((flags & 2) && !d_flux_mirror) {  // each non-owner face slot -> the owner's slot of that face
     const size_t S = (size_t)topo.wf * N;
     size_t nfaces = 0;  // unused slots hold 0xFFFFFFFF: not a face

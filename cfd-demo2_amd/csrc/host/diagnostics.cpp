@@ -59,7 +59,7 @@ void Solver::flow_diag_device(bool fields, bool reduce) {
   unsigned long long* mx = reinterpret_cast<unsigned long long*>(diag_res + 6);
   // prescribed boundary velocities: the moving walls' face values and relative velocity
   const BcvArgs v = bcv.args();
-  launch_flow_diag(a, bcv.on() ? &v : nullptr, mx, stream);
+  launch_flow_diag(a, bcv.on() ? &v : nullptr, visc.mu, mx, stream);
   if (!reduce) {  // derived fields only: nothing to reduce across ranks, not collective
     check_launch("flow diagnostics (fields)");
     return;

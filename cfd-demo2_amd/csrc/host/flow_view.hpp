@@ -1,5 +1,5 @@
 // What an opt-in feature (the post-processing modules of modules.hpp, Scalars,
-// BoundaryVelocity) may read of the solver: one value, built fresh by
+// BoundaryVelocity, Viscosity) may read of the solver: one value, built fresh by
 // Solver::view for every call (the ring rotates), of const members and
 // pointers to const.  A method of theirs takes it first and has no other way
 // to the solver's state.
@@ -85,6 +85,7 @@ struct FlowView {
   const float last_step_dt;       // 0: no step yet
   const BcvArgs bcv_args;         // prescribed boundary velocities; through bcv()
   const bool bcv_on;
+  const float* const visc_mu;     // [N] the viscosity per cell (viscosity.hpp), or null: constants.viscosity
   const uint64_t surface_gen;     // grows with every change of the scalar or boundary-velocity configuration
   const bool check_sync;
   // nf, field, bcv_args and bcv_on are copies for the post-processing modules.

@@ -215,8 +215,8 @@ FlowView Solver::view(const char* one_gpu_message) const {
                   NG,               topo.ld,          fs,              d_vol,
                   flux_s,           sums(),           constants,       ring[i_state].u,
                   ring[i_state].p,  scalars.s.count,  {field(0), field(1), field(2), field(3)},
-                  last_step_dt,     bcv.args(),       bcv.on(),        scalars.gen + bcv.gen,
-                  check_sync};
+                  last_step_dt,     bcv.args(),       bcv.on(),        visc.mu,
+                  scalars.gen + bcv.gen,             check_sync};
 }
 
 Solver::~Solver() {
@@ -238,6 +238,7 @@ Solver::~Solver() {
   arena.release();
   bcv.arena.release();
   bcv.wm_arena.release();
+  visc.arena.release();
   amg_arena.release();
   scalars.arena.release();
   if (cstream) (void)hipStreamDestroy(cstream);
@@ -358,8 +359,11 @@ void Solver::prepare() {
     check_launch("prepare (reference semantics)");
     return;
   }
-  if (bcv.on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
-    launch_prepare_bcv(a, bcv.args(), stream);
+  const BcvArgs v = bcv.args();
+  if (visc.on())  // variable viscosity (viscosity.cpp): the VISC forms only with a field
+    launch_prepare_visc(a, bcv.on() ? &v : nullptr, visc.mu, stream);
+  else if (bcv.on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
+    launch_prepare_bcv(a, v, stream);
   else
     launch_prepare(a, stream);
   check_launch("prepare");
@@ -396,8 +400,11 @@ void Solver::assemble() {
   // and g != 0; otherwise the plain kernel with the arguments it always had
   BuoyancyArgs b;
   const bool buoyant = scalars.buoyancy_args(b);
-  if (bcv.on())  // prescribed boundary velocities: the BCV form of either
-    launch_assemble_bcv(a, buoyant ? &b : nullptr, bcv.args(), stream);
+  const BcvArgs v = bcv.args();
+  if (visc.on())  // variable viscosity: the VISC form of any of the four
+    launch_assemble_visc(a, buoyant ? &b : nullptr, bcv.on() ? &v : nullptr, visc.mu, stream);
+  else if (bcv.on())  // prescribed boundary velocities: the BCV form of either
+    launch_assemble_bcv(a, buoyant ? &b : nullptr, v, stream);
   else if (buoyant)
     launch_assemble_buoyant(a, b, stream);
   else
@@ -512,6 +519,7 @@ void Solver::step() {  // coupled_solver.rs:33-499
   const int fault_rank = debug_fault_after_prepare;  // test hook, one step only
   debug_fault_after_prepare = -1;
   if (dist()) halo_state(true);  // the rotated slot's ghosts (last written 3 steps ago)
+  if (visc.has_model()) visc.evaluate(view(nullptr));  // the step's viscosity, from the velocity it starts from
   prepare();
   if (fault_rank == rk) throw std::runtime_error("injected fault after prepare");
   const bool fixed = cfg.fixed_outer > 0;

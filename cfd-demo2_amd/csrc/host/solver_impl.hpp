@@ -22,6 +22,7 @@
 #include "scalars.hpp"
 #include "topology.hpp"
 #include "tuning.hpp"
+#include "viscosity.hpp"
 
 namespace cfd2 {
 
@@ -456,16 +457,18 @@ struct Solver {
   void get_derived(int kind, double* out);
   uint32_t set_force_region(double x0, double y0, double x1, double y1);
   float adapt_dt(double target_cfl);
-  // ---- the opt-in physics (scalars.hpp, boundary_velocity.hpp) ----
+  // ---- the opt-in physics (scalars.hpp, boundary_velocity.hpp, viscosity.hpp) ----
   // Each reads the solver through view() alone.  step() asks them for kernel
-  // arguments (scalars.buoyancy_args, bcv.on / bcv.args) and only records the
-  // dt it used (last_step_dt).
+  // arguments (scalars.buoyancy_args, bcv.on / bcv.args, visc.on / visc.mu) and
+  // only records the dt it used (last_step_dt).
   Scalars scalars;
   BoundaryVelocity bcv;
+  Viscosity visc;
   std::vector<double> cell_cx, cell_cy;  // f64 cell centres (one GPU only: Scalars::set_source's box)
   float last_step_dt = 0.0f;             // the dt of the last step(); 0: no step yet
   // what BoundaryVelocity's calls refuse first: ref_racy stays private
   void bcv_need(const char* what) const { BoundaryVelocity::need(what, dist(), ref_racy); }
+  void visc_need(const char* what) const { Viscosity::need(what, dist(), ref_racy || ref_inplace); }
   // ---- the opt-in post-processing modules (modules.hpp) ----
   // Each reads the solver through view() alone; nothing of theirs is allocated
   // before their first enabling call, and step() launches none of it.

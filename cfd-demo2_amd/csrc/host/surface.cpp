@@ -140,7 +140,7 @@ void SurfaceDist::sample(const FlowView& flow, double* sample_out) {
   const Range range("surface sample");
   CFD_HIP(hipSetDevice(flow.device));
   const SurfaceArgs a = args(flow);
-  launch_surface_sample(a, flow.bcv(), flow.stream);
+  launch_surface_sample(a, flow.bcv(), flow.visc_mu, flow.stream);
   flow.check_launch("surface sample");
   CFD_HIP(hipMemcpy2DAsync(sample_out, n * sizeof(double), out, ld * sizeof(double), n * sizeof(double), nch,
                            hipMemcpyDeviceToHost, flow.stream));
@@ -181,7 +181,7 @@ void SurfaceDist::stats_accumulate(const FlowView& flow, double weight) {
   SurfaceArgs a = args(flow);
   a.w = weight;
   a.r = weight / Wn;
-  launch_surface_accumulate(a, flow.bcv(), flow.stream);
+  launch_surface_accumulate(a, flow.bcv(), flow.visc_mu, flow.stream);
   flow.check_launch("surface statistics");
   W = Wn;
   samples += 1;

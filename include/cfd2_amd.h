@@ -1044,6 +1044,107 @@ cfd_status cfd_boundary_velocity_get(const cfd_solver* s, cfd_boundary_velocity*
 cfd_status cfd_wall_motion_get(cfd_solver* s, double x0, double y0, cfd_wall_motion* out);
 
 /* ------------------------------------------------------------------------ */
+/* Variable viscosity: a viscosity per cell.  Without it the fluid has one
+ * viscosity, cfd_constants::viscosity, in every face's diffusion coefficient.
+ * cfd_set_viscosity_field gives every cell a viscosity of its own: the
+ * mechanism a generalised Newtonian fluid (power law, Carreau), an eddy
+ * viscosity or a temperature-dependent viscosity needs.  The caller uploads a
+ * field of its own, once or before every step, or sets one of the models
+ * below (cfd_set_viscosity_model), which the device evaluates every step.
+ * Opt-in: without a field (the default, and again after a clear) cfd_step
+ * launches the kernels it always launched, with the same arguments, and
+ * produces the same bits; with one, prepare_coupled, the assembly, the flow
+ * diagnostics, cfd_wall_motion_get and the surface run in their VISC forms,
+ * which read one more coalesced 4-byte value per cell and gather one 4-byte
+ * value per interior face slot, beside the neighbour's velocity.
+ *
+ * Arithmetic of variable viscosity.  All f32, one rounding per operation
+ * (nothing fused).  With the uploaded mu[N], for face slot k of cell i whose
+ * neighbour across the face is cell o:
+ *   interior slot   mu_f = 0.5f * (mu[i] + mu[o])
+ *   boundary slot   mu_f = mu[i]
+ * The arithmetic mean is commutative in floating point: both cells of a face
+ * form the same bits, so the diffusion part of the matrix stays symmetric bit
+ * for bit.  mu_f replaces cfd_constants::viscosity and nothing else: in
+ * prepare_coupled (the diagonal that gives d_p) and in the assembly (the
+ * diagonal, the off-diagonal entry -diff_coeff + min(flux, 0), the boundary
+ * terms diff_coeff * ub)
+ *   diff_coeff = mu_f * area / dist
+ * with each kernel's own distance as before: |centre - other centre| (|centre -
+ * face centre| on a boundary slot) in prepare_coupled, max(|d . n|, 1e-6) in
+ * the assembly.  A uniform field equal to cfd_constants::viscosity gives the
+ * plain kernels' bits: 0.5f * (m + m) == m exactly.
+ * Flow diagnostics, cfd_wall_motion_get and the surface channels 3 and 4: the
+ * viscous force of a wall face of cell i is, in f64,
+ *   (double)mu[i] * u_rel * area / dist
+ * in place of (double)viscosity * u_rel * area / dist (u_rel: the velocity
+ * relative to the wall, "Arithmetic of boundary velocities").
+ * The pointer the kernels read stays the same while a field is set, and they
+ * read its contents when they run: replacing the field between steps costs one
+ * upload, also when the Krylov iteration replays a captured graph
+ * (cfd_graph_enable); prepare_coupled and the assembly are launched by the step
+ * itself.  The field takes effect at the next cfd_step.
+ * Checkpoints do not store the field (the file format and its version are
+ * unchanged): a resumed run sets it again.  One GPU only, and not together with
+ * flags 1 or 2 of cfd_debug_reference_semantics.                             */
+/* n == num_cells: enables the field or replaces its values; n == 0 clears it
+ * (mu may be null).  CFD_ERR_INVALID: any other n, a value that is not finite
+ * or not > 0, a distributed handle, reference semantics with flag 1 or 2.  A
+ * refused call changes nothing.                                              */
+cfd_status cfd_set_viscosity_field(cfd_solver* s, const float* mu, uint32_t n);
+/* out[num_cells]: the field the next cfd_step will read (and, unless it was
+ * replaced since, the last one did).  CFD_ERR_INVALID: no field is set.       */
+cfd_status cfd_get_viscosity_field(cfd_solver* s, float* out);
+/* The viscosity models: generalised Newtonian fluids evaluated on the device.
+ * With a model set, cfd_step evaluates it once, before the first Picard
+ * iteration, from the velocity the step starts from, and the whole step reads
+ * that field (first-order lagging, the splitting stance of buoyancy).
+ *
+ * Arithmetic of the viscosity models.  Per cell, the Green-Gauss gradients
+ * (ux, uy) of u and (vx, vy) of v of the CURRENT velocity exactly as
+ * prepare_coupled forms them (its face values, those of "Arithmetic of
+ * boundary velocities" with a selection on; not the gradients a previous step
+ * left), so the field is a function of the state alone.  Then, every operation
+ * one rounding in this order, the parameters widened from f32:
+ *   f32  gdot = sqrtf(2*(ux*ux) + 2*(vy*vy) + (uy+vx)*(uy+vx))
+ *   f64  power law (kind 1)  m = K * pow_det(max(gdot, gamma_min), n - 1)
+ *   f64  Carreau   (kind 2)  m = mu_inf + (mu0 - mu_inf) * pow_det(1 + (lambda*gdot)*(lambda*gdot), (n - 1) / 2)
+ *   f32  mu = (float) min(max(m, mu_min), mu_max)
+ * pow_det(x, y) = x^y from IEEE + - * /, frexp, ldexp and rint alone, the same
+ * bits on the host and the device (csrc/hip/pow_det.hpp states the series, the
+ * term counts and the error bound (16 + 8 |y ln x|) 2^-53).  A cell counts as
+ * clamped below when m < mu_min and above when m > mu_max.
+ * cfd_set_viscosity_model enables the field (evaluating the model on the
+ * current state at once); cfd_set_viscosity_field and clearing the field clear
+ * the model; kind 0 clears the model and leaves the field as it stands.
+ * Checkpoints store neither: a resumed run sets the model again, and because
+ * the field is a function of the state its next step has the bits of the
+ * uninterrupted run.  One GPU only; not with reference-semantics flags 1, 2.   */
+typedef struct cfd_viscosity_model {
+  int32_t kind;     /* 0 none, 1 power law, 2 Carreau */
+  float K, n;       /* power law: consistency K > 0, index n; Carreau reads n too */
+  float gamma_min;  /* power law: > 0, the shear rate below which the law is cut off */
+  float mu0, mu_inf, lambda; /* Carreau: mu0 > 0, mu_inf >= 0, lambda > 0 */
+  float mu_min, mu_max;      /* 0 < mu_min <= mu_max, both finite */
+} cfd_viscosity_model;
+typedef struct cfd_viscosity_stats {
+  float mu_min, mu_max;     /* over the cells, of the last evaluation */
+  uint32_t clamped_below, clamped_above;
+} cfd_viscosity_stats;
+/* CFD_ERR_INVALID: an unknown kind, a parameter of the chosen kind that is not
+ * finite or outside the ranges above, mu_min > mu_max, a distributed handle,
+ * reference semantics with flag 1 or 2.  A refused call changes nothing.      */
+cfd_status cfd_set_viscosity_model(cfd_solver* s, const cfd_viscosity_model* model);
+/* Evaluates the model on the current state now (cfd_step does it by itself).
+ * CFD_ERR_INVALID for this and the two below: no model is set.                */
+cfd_status cfd_viscosity_evaluate(cfd_solver* s);
+/* out[num_cells]: gdot of the last evaluation.                               */
+cfd_status cfd_get_shear_rate(cfd_solver* s, float* out);
+cfd_status cfd_viscosity_stats_get(cfd_solver* s, cfd_viscosity_stats* out);
+/* Test-only: out[i] = pow_det(x[i], y[i]) by the host copy of csrc/hip/pow_det.hpp. */
+cfd_status cfd_debug_pow_det(const double* x, const double* y, double* out, uint32_t n);
+
+/* ------------------------------------------------------------------------ */
 /* Frames on the device: a cell field as an H x W RGBA8 image, the headless
  * form of the reference's renderer (src/ui/cfd_renderer.rs fan-triangulates
  * every cell, cfd_mesh_shader.wgsl colours each fan by the cell's value).  The
