@@ -3,7 +3,7 @@
 
 Python mirror of the reference API over the C ABI in include/cfd2_amd.h.
 """
-from . import image, mesh, surface  # noqa: F401
+from . import image, mesh, penalty, surface  # noqa: F401
 from .mesh import (BackwardsStep, ChannelWithObstacle, CircleObstacle, Mesh,  # noqa: F401
                    RectangularChannel, generate_cut_cell_mesh)
 from .solver import (GpuGroup, GpuSolver, adaptive_dt_rule, dist_plan, dist_unique_id,  # noqa: F401,E402

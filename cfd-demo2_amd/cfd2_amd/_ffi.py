@@ -258,6 +258,16 @@ class ViscosityStats(C.Structure):  # cfd_viscosity_stats
                 ("clamped_above", C.c_uint32)]
 
 
+class PenaltyInfo(C.Structure):  # cfd_penalty_info
+    _fields_ = [("active", C.c_int32), ("has_forch", C.c_int32), ("has_target", C.c_int32),
+                ("target_scale", C.c_float), ("max_vol_sigma", C.c_double)]
+
+
+class PenaltyForce(C.Structure):  # cfd_penalty_force
+    _fields_ = [("force", C.c_double * 2), ("torque", C.c_double), ("power", C.c_double), ("cells", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class WallMotion(C.Structure):  # cfd_wall_motion
     _fields_ = [("torque_pressure", C.c_double), ("torque_viscous", C.c_double), ("power", C.c_double),
                 ("region_faces", C.c_uint32), ("moving_faces", C.c_uint32)]
@@ -414,6 +424,7 @@ EXPORTED = [
     "cfd_wall_motion_get",
     "cfd_set_viscosity_field", "cfd_get_viscosity_field", "cfd_set_viscosity_model", "cfd_viscosity_evaluate",
     "cfd_get_shear_rate", "cfd_viscosity_stats_get", "cfd_debug_pow_det",
+    "cfd_set_penalty", "cfd_set_penalty_scale", "cfd_get_penalty", "cfd_penalty_force_get",
     "cfd_particles_set_mesh", "cfd_particle_config_default", "cfd_particles_enable", "cfd_particles_seed",
     "cfd_particles_advance", "cfd_particles_get", "cfd_particles_stats_get", "cfd_render_particles",
     "cfd_tstats_enable", "cfd_tstats_disable", "cfd_tstats_reset", "cfd_tstats_accumulate", "cfd_tstats_info",

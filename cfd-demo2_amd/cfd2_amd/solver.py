@@ -21,6 +21,10 @@ BuoyancyForce = collections.namedtuple("BuoyancyForce", "fx fy fields")
 # GpuSolver.wall_motion(): torques of the pressure and viscous force on the force
 # region's walls, the power its selected moving walls deliver, and the face counts
 WallMotion = collections.namedtuple("WallMotion", "torque_pressure torque_viscous power region_faces moving_faces")
+# GpuSolver.penalty_force(): the force of the fluid on the penalised medium, its torque, the rate
+# of work of that force on the moving medium (negative where the body drives the fluid) and the
+# number of penalised cells
+PenaltyForce = collections.namedtuple("PenaltyForce", "force torque power cells")
 # GpuSolver.particles(): float32 x, y and age, uint32 cell and status (CFD_PARTICLE_*), one entry per slot
 Particles = collections.namedtuple("Particles", "x y cell status age")
 
@@ -156,6 +160,10 @@ def _bind():
     L.cfd_viscosity_stats_get.argtypes = [_vp, C.POINTER(_ffi.ViscosityStats)]
     dp_ = C.POINTER(C.c_double)
     L.cfd_debug_pow_det.argtypes = [dp_, dp_, dp_, C.c_uint32]
+    L.cfd_set_penalty.argtypes = [_vp, fp, fp, fp, C.c_uint32]
+    L.cfd_set_penalty_scale.argtypes = [_vp, C.c_float]
+    L.cfd_get_penalty.argtypes = [_vp, C.POINTER(_ffi.PenaltyInfo), fp, fp, fp]
+    L.cfd_penalty_force_get.argtypes = [_vp, C.c_double, C.c_double, dp_, C.POINTER(_ffi.PenaltyForce)]
     L.cfd_render_set_polygons.argtypes = [_vp, C.c_uint32, dp, dp, u32p, u32p]
     L.cfd_render_set_view.argtypes = [_vp, C.c_int32, C.c_int32, dp, u32p]
     L.cfd_render.argtypes = [_vp, C.c_int32, C.c_int32, fp, u8p, fp]
@@ -703,6 +711,68 @@ class GpuSolver:
         self._call("cfd_viscosity_stats_get", C.byref(st))
         return dict(mu_min=float(st.mu_min), mu_max=float(st.mu_max), clamped_below=int(st.clamped_below),
                     clamped_above=int(st.clamped_above))
+
+    # -- volume penalisation: porous zones and immersed bodies ----------------------
+    def set_penalty(self, sigma, forch=None, target=None) -> None:
+        """cfd_set_penalty: ``sigma`` [num_cells] >= 0, the linear drag
+        coefficient of each cell in  -s (u - u_t),  s = sigma + forch |u|;
+        ``forch`` [num_cells] >= 0 or None; ``target`` [num_cells, 2], the
+        velocity u_t the drag pulls towards, or None (rest).  All rounded to
+        float32.  Sets the field or replaces its values (one upload; nothing is
+        re-captured); takes effect at the next step().  Refused above the
+        handle's limit on vol * sigma (``penalty()["max_vol_sigma"]``).  Not
+        stored in a checkpoint.  One GPU only.  penalty.py builds fields."""
+        f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1).astype(np.float32))  # noqa: E731
+        fp = C.POINTER(C.c_float)
+        sg = f32(sigma)
+        if len(sg) == 0:
+            raise ValueError("an empty penalty field: clear_penalty() clears it")
+        fo = None if forch is None else f32(forch)
+        tg = None if target is None else f32(target)
+        if (fo is not None and len(fo) != len(sg)) or (tg is not None and len(tg) != 2 * len(sg)):
+            raise ValueError("penalty: forch [n] and target [n, 2] must match sigma [n]")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(fp)  # noqa: E731
+        self._call("cfd_set_penalty", ptr(sg), ptr(fo), ptr(tg), len(sg))
+
+    def clear_penalty(self) -> None:
+        """The next step() runs the kernels it ran before the field was set."""
+        self._call("cfd_set_penalty", None, None, None, 0)
+
+    def set_penalty_scale(self, s) -> None:
+        """cfd_set_penalty_scale: the factor on the target velocity, a kernel
+        argument (an oscillating body costs no upload)."""
+        self._call("cfd_set_penalty_scale", float(s))
+
+    def penalty(self) -> dict:
+        """cfd_get_penalty: active (False on a rank handle and in the reference-
+        semantics modes, where no field can be set), target_scale, max_vol_sigma and, with a field
+        set, the float32 sigma, forch (or None) and target [n, 2] (or None)."""
+        info = _ffi.PenaltyInfo()
+        self._call("cfd_get_penalty", C.byref(info), None, None, None)
+        out = dict(active=bool(info.active), target_scale=float(info.target_scale),
+                   max_vol_sigma=float(info.max_vol_sigma), sigma=None, forch=None, target=None)
+        if info.active:
+            fp = C.POINTER(C.c_float)
+            n = self.num_cells
+            sg = np.empty(n, np.float32)
+            fo = np.empty(n, np.float32) if info.has_forch else None
+            tg = np.empty((n, 2), np.float32) if info.has_target else None
+            ptr = lambda a: None if a is None else a.ctypes.data_as(fp)  # noqa: E731
+            self._call("cfd_get_penalty", None, ptr(sg), ptr(fo), ptr(tg))
+            out.update(sigma=sg, forch=fo, target=tg)
+        return out
+
+    def penalty_force(self, centre=(0.0, 0.0), box=None) -> PenaltyForce:
+        """cfd_penalty_force_get: the force of the fluid on the penalised medium,
+        its torque about ``centre``, the rate of work of that force on the moving
+        medium (``power``: negative where the body drives the fluid, which then
+        receives ``-power``) and the number of penalised cells, over the cells whose centre lies in ``box`` (x0, y0,
+        x1, y1; None: every cell), on the current state.  Read-only."""
+        b = None if box is None else (C.c_double * 4)(*[float(v) for v in box])
+        out = _ffi.PenaltyForce()
+        self._call("cfd_penalty_force_get", float(centre[0]), float(centre[1]), b, C.byref(out))
+        return PenaltyForce((float(out.force[0]), float(out.force[1])), float(out.torque), float(out.power),
+                            int(out.cells))
 
     # -- frames on the device: a cell field as an RGBA8 image ---------------------
     def set_render_mesh(self, mesh) -> None:

@@ -9,6 +9,14 @@ namespace cfd2 {
 
 namespace {
 
+// Volume penalisation (kernels.hpp PenaltyArgs): pen = vol * s of cell i from
+// the iterate uc; the forch test is on a kernel argument, uniform over the launch.
+__device__ __forceinline__ float penalty_coeff(const PenaltyArgs& pn, float vol, float2 uc, uint32_t i) {
+  float s = pn.sigma[i];
+  if (pn.forch) s = s + pn.forch[i] * sqrtf(uc.x * uc.x + uc.y * uc.y);
+  return vol * s;
+}
+
 // ---------------------------------------------------------------------------
 // prepare_coupled.wgsl:63-348 — Rhie-Chow face flux, d_p, Green-Gauss grads.
 // Snapshot semantics: reads st (pre-kernel), writes d_p/grad_p to dp_out/gp_out.
@@ -21,10 +29,13 @@ namespace {
 // one more coalesced 4-byte load per cell and one 4-byte gather per interior
 // slot, beside the u[other] gathers; the face viscosity stands where
 // c.viscosity stood and nothing else changes.
-template <bool BCV, bool VISC>
+// PEN: the form with volume penalisation (kernels.hpp PenaltyArgs): after the
+// face loop the diagonal takes vol * s, so d_p sees the drag; one to two more
+// coalesced 4-byte loads per cell, no gather.
+template <bool BCV, bool VISC, bool PEN = false>
 __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs& v, const float* __restrict__ mu,
                                              uint32_t i, float& dp_new, float2& gp_new, float2& gu_new,
-                                             float2& gv_new) {
+                                             float2& gv_new, const PenaltyArgs& pn = PenaltyArgs{}) {
   const uint32_t N = a.N;
   const cfd_constants c = a.c;
   const FaceSlots fs = a.fs;
@@ -166,6 +177,7 @@ __device__ __forceinline__ void prepare_cell(const PrepareArgs& a, const BcvArgs
     gvx += vfv * nx * area;
     gvy += vfv * ny * area;
   }
+  if constexpr (PEN) diag_coeff += penalty_coeff(pn, vol, uc, i);
   dp_new = (fabsf(diag_coeff) > 1e-20f) ? vol / diag_coeff : 0.0f;
   gp_new = make_float2(gpx / vol, gpy / vol);
   gu_new = make_float2(gux / vol, guy / vol);
@@ -215,6 +227,20 @@ __global__ void __launch_bounds__(kBlock) k_prepare_bcv_visc(PrepareArgs a, BcvA
   a.grad_u[i] = gu;
   a.grad_v[i] = gv;
 }
+// the PEN forms: every argument struct, the unused ones empty
+template <bool BCV, bool VISC>
+__global__ void __launch_bounds__(kBlock) k_prepare_pen(PrepareArgs a, BcvArgs v, const float* __restrict__ mu,
+                                                        PenaltyArgs pn) {
+  const uint32_t i = row_id();
+  if (i >= a.N) return;
+  float dp;
+  float2 gp, gu, gv;
+  prepare_cell<BCV, VISC, true>(a, v, mu, i, dp, gp, gu, gv, pn);
+  a.dp_out[i] = dp;
+  a.gp_out[i] = gp;
+  a.grad_u[i] = gu;
+  a.grad_v[i] = gv;
+}
 // The reference's RACY prepare (prepare_coupled.wgsl:140-143 vs :328-337)
 // under one legal schedule (test mode, Solver::ref_racy; oracle
 // kSemRacyPrepare): the 64-cell workgroups one after another, d_p / grad_p
@@ -255,9 +281,12 @@ __global__ void __launch_bounds__(kBlock) k_flux_mirror(float* flux_s, const int
 // prepare_cell: nothing is added to an interior slot.
 // VISC: the form with a viscosity per cell, as in prepare_cell, with this
 // kernel's own distance (dist_a); the gather sits beside dp[other].
-template <bool BUOY, bool BCV, bool VISC>
+// PEN: the form with volume penalisation (kernels.hpp PenaltyArgs): after the
+// face loop and the BUOY block the diagonal takes vol * s and, with a target,
+// the right-hand side vol * s * (target_scale * target); no off-diagonal changes.
+template <bool BUOY, bool BCV, bool VISC, bool PEN = false>
 __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const BuoyancyArgs b, const BcvArgs v,
-                                              const float* __restrict__ mu) {
+                                              const float* __restrict__ mu, const PenaltyArgs pn = PenaltyArgs{}) {
   const uint32_t i = row_id();
   const uint32_t N = a.N;
   if (i >= N) return;
@@ -426,6 +455,15 @@ __device__ __forceinline__ void assemble_cell(const AssembleArgs a, const Buoyan
       }
     }
   }
+  if constexpr (PEN) {
+    const float pen = penalty_coeff(pn, vol, uc, i);
+    diag_uv += pen;
+    if (pn.target) {
+      const float2 ut = pn.target[i];
+      rhs_u += pen * (pn.target_scale * ut.x);
+      rhs_v += pen * (pn.target_scale * ut.y);
+    }
+  }
   const size_t cdslot = (size_t)a.cslot_diag[i] * a.ld + i;
   a.cval_a[cdslot] = make_float2(diag_uv, 0.0f + sdpp);
   a.cval_g[cdslot] = make_float2(sdup, sdvp);
@@ -462,6 +500,11 @@ __global__ void __launch_bounds__(kBlock) k_assemble_bcv_visc(AssembleArgs a, Bc
 __global__ void __launch_bounds__(kBlock) k_assemble_buoyant_bcv_visc(AssembleArgs a, BuoyancyArgs b, BcvArgs v,
                                                                       const float* __restrict__ mu) {
   assemble_cell<true, true, true>(a, b, v, mu);
+}
+template <bool BUOY, bool BCV, bool VISC>
+__global__ void __launch_bounds__(kBlock) k_assemble_pen(AssembleArgs a, BuoyancyArgs b, BcvArgs v,
+                                                         const float* __restrict__ mu, PenaltyArgs pn) {
+  assemble_cell<BUOY, BCV, VISC, true>(a, b, v, mu, pn);
 }
 
 // update_fields_from_coupled.wgsl:45-98.  The reference folds max|du|, max|dp|
@@ -579,6 +622,35 @@ void launch_assemble_visc(const AssembleArgs& a, const BuoyancyArgs* buoy, const
     hipLaunchKernelGGL(k_assemble_buoyant_visc, g, b, 0, s, a, *buoy, mu);
   else
     hipLaunchKernelGGL(k_assemble_visc, g, b, 0, s, a, mu);
+}
+void launch_prepare_pen(const PrepareArgs& a, const BcvArgs* v, const float* mu, const PenaltyArgs& pn, hipStream_t s) {
+  if (!a.N) return;
+  const BcvArgs vv = v ? *v : BcvArgs{};
+  auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, vv, mu, pn); };
+  if (v && mu)
+    go(k_prepare_pen<true, true>);
+  else if (v)
+    go(k_prepare_pen<true, false>);
+  else if (mu)
+    go(k_prepare_pen<false, true>);
+  else
+    go(k_prepare_pen<false, false>);
+}
+void launch_assemble_pen(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs* v, const float* mu,
+                         const PenaltyArgs& pn, hipStream_t s) {
+  if (!a.N) return;
+  const BuoyancyArgs bb = buoy ? *buoy : BuoyancyArgs{};
+  const BcvArgs vv = v ? *v : BcvArgs{};
+  auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(grid_for(a.N)), dim3(kBlock), 0, s, a, bb, vv, mu, pn); };
+  auto visc = [&](auto with, auto without) { mu ? go(with) : go(without); };
+  if (buoy && v)
+    visc(k_assemble_pen<true, true, true>, k_assemble_pen<true, true, false>);
+  else if (buoy)
+    visc(k_assemble_pen<true, false, true>, k_assemble_pen<true, false, false>);
+  else if (v)
+    visc(k_assemble_pen<false, true, true>, k_assemble_pen<false, true, false>);
+  else
+    visc(k_assemble_pen<false, false, true>, k_assemble_pen<false, false, false>);
 }
 void launch_update_fields(uint32_t N, float au, float ap, const float* x, float2* u, float* p,
                           uint32_t* blockmax, uint32_t* maxbits, uint32_t* host_out, hipStream_t s) {

@@ -394,6 +394,55 @@ void launch_assemble_bcv(const AssembleArgs& a, const BuoyancyArgs* buoy, const 
 void launch_prepare_visc(const PrepareArgs& a, const BcvArgs* v, const float* mu, hipStream_t s);
 void launch_assemble_visc(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs* v, const float* mu,
                           hipStream_t s);
+// Volume penalisation (include/cfd2_amd.h "Arithmetic of volume penalisation" is
+// the contract), one more kernel argument of the PEN forms only: a linear drag
+// towards a target velocity, diagonal and implicit.  Per cell i, all f32, one
+// rounding per operation, uc = st.u[i] (the iterate both kernels already load):
+//   s   = sigma[i]                                              forch null
+//   s   = sigma[i] + forch[i] * sqrtf(uc.x*uc.x + uc.y*uc.y)    forch set
+//   pen = vol[i] * s
+//   prepare : diag_coeff += pen     after the face loop, before dp_new
+//   assemble: diag_uv    += pen     after the face loop and the BUOY block
+//             rhs_u += pen * (target_scale * target[i].x)       target set; null: nothing is added
+//             rhs_v += pen * (target_scale * target[i].y)
+// forch and target are tested as kernel arguments: uniform over the launch (as
+// k_wall_motion tests mu).  One more coalesced 4-byte load per cell, 4 more with
+// forch, 8 more with target; no gather.  The PEN forms are one templated
+// __global__ per stage, every argument struct present and the unused ones
+// empty; v / mu / buoy: null for the forms without them.
+struct PenaltyArgs {
+  const float* sigma;    // [N]
+  const float* forch;    // [N] or null
+  const float2* target;  // [N] or null
+  float target_scale;
+};
+void launch_prepare_pen(const PrepareArgs& a, const BcvArgs* v, const float* mu, const PenaltyArgs& pn, hipStream_t s);
+void launch_assemble_pen(const AssembleArgs& a, const BuoyancyArgs* buoy, const BcvArgs* v, const float* mu,
+                         const PenaltyArgs& pn, hipStream_t s);
+// ---- penalty.hip ----
+// Read-only diagnostic of the penalisation: the force of the fluid on the
+// penalised medium, its torque about (x0, y0), the rate of work of that force on the moving medium and
+// the number of penalised cells, over the cells whose f64 centre ctr[i] lies in
+// the closed box (box_on; the force region's rule: none for x1 < x0).  Per cell,
+// in f64, every f32 value widened first, one rounding per operation:
+//   s  = sigma (+ forch * sqrt(ux*ux + uy*uy))      forch set
+//   m  = vol * s;  tx = scale * target.x, ty = scale * target.y   (0, 0 with target null)
+//   fx = m * (ux - tx);  fy = m * (uy - ty)
+//   sums: fx, fy, rx * fy - ry * fx (r = ctr[i] - (x0, y0)), fx * tx + fy * ty, s > 0 ? 1 : 0
+// Unit partials partial[c * np + unit] in the canonical tree.
+constexpr int kPenaltySums = 5;
+struct PenaltyForceArgs {
+  uint32_t N;
+  const float* vol;
+  const float2* u;
+  PenaltyArgs pn;
+  const double2* ctr;  // [N]
+  double x0, y0;
+  int32_t box_on;
+  double box[4];       // x0, y0, x1, y1
+  SumOut out;          // [kPenaltySums * np]
+};
+void launch_penalty_force(const PenaltyForceArgs& a, hipStream_t s);
 // ---- viscosity.hip ----
 // The viscosity models (include/cfd2_amd.h "Arithmetic of the viscosity
 // models"): per cell the Green-Gauss gradients of u as prepare_cell forms them,

@@ -89,10 +89,14 @@ double Solver::layout_step_bytes() const {
   // the VISC forms (viscosity.hpp): mu per cell, 4 B.  The gather mu[other] of every internal slot adds nothing:
   // as with the u / dp gathers here, each cell's value is counted once and the re-reads are assumed to hit cache
   const double visc_bytes = visc.on() ? 4.0 * Nn : 0.0;
-  const double prep = 40 * S + 60 * Nn + visc_bytes;       // 9 slot arrays + flux out; cell state in, gradients out
+  // the PEN forms (penalty.hpp): sigma 4 B, forch 4 B and the target 8 B per cell when set, coalesced, no gather;
+  // prepare reads sigma and forch, the assembly the target too
+  const double pen_prep = pen.on() ? (4.0 + (pen.has_forch ? 4.0 : 0.0)) * Nn : 0.0;
+  const double pen_asmb = pen.on() ? pen_prep + (pen.has_target ? 8.0 : 0.0) * Nn : 0.0;
+  const double prep = 40 * S + 60 * Nn + visc_bytes + pen_prep;  // 9 slot arrays + flux out; cell state in, gradients out
   BuoyancyArgs bu;
   const double buoy = scalars.buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // the buoyant assembly: one field value per driving field
-  const double asmb = 32 * S + 20 * Sint + 78 * Nn + buoy + visc_bytes;  // 8 slot arrays; 3x3 block + Poisson entry out
+  const double asmb = 32 * S + 20 * Sint + 78 * Nn + buoy + visc_bytes + pen_asmb;  // 8 slot arrays; 3x3 block + Poisson entry out
   const double spmv = (35 + 16 * ws) * Nn;                 // headers, cval_a + cval_g slots, x, y
   const double predict = (39 + 8 * ws) * Nn;               // headers, cval_g slots, V_j, dinv, temp_p / p_sol out
   const double correct = (34 + 8 * ws) * Nn;               // lg, cval_g slots, p_sol, V_j, dinv, Z_j out
@@ -114,10 +118,12 @@ double Solver::algorithmic_step_bytes() const {
   const double nnz_s = S;
   // a viscosity per cell: 4 B per cell and 4 B per face (the neighbour's) in prepare and in assemble
   const double visc_bytes = visc.on() ? 4.0 * Nn + 4.0 * Sfaces : 0.0;
-  const double prep = 84 * Nn + 4 * Sfaces + 36 * Fn + visc_bytes;
+  const double pen_prep = pen.on() ? (4.0 + (pen.has_forch ? 4.0 : 0.0)) * Nn : 0.0;  // as in layout_step_bytes
+  const double pen_asmb = pen.on() ? pen_prep + (pen.has_target ? 8.0 : 0.0) * Nn : 0.0;
+  const double prep = 84 * Nn + 4 * Sfaces + 36 * Fn + visc_bytes + pen_prep;
   BuoyancyArgs bu;
   const double buoy = scalars.buoyancy_args(bu) ? 4.0 * bu.n * Nn : 0.0;  // as in layout_step_bytes
-  const double asmb = 68 * Nn + 8 * Sfaces + 36 * Fn + 40 * nnz_s + buoy + visc_bytes;
+  const double asmb = 68 * Nn + 8 * Sfaces + 36 * Fn + 40 * nnz_s + buoy + visc_bytes + pen_asmb;
   const int K = cfg.fixed_outer > 0 ? cfg.fixed_outer : std::max(cfg.n_outer_correctors, 10);
   const int M = cfg.fixed_inner > 0 ? std::min(cfg.fixed_inner, m) : m;
   // V-cycle bytes

@@ -743,6 +743,48 @@ cfd_status cfd_debug_pow_det(const double* x, const double* y, double* out, uint
   return CFD_OK;
 }
 
+// ------------------------------------------------------- volume penalisation
+cfd_status cfd_set_penalty(cfd_solver* s, const float* sigma, const float* forch, const float* target, uint32_t n) {
+  CHECK_S(s);
+  if (n && !sigma) return set_error(CFD_ERR_INVALID, "null sigma");
+  return guard([&] {
+    cfd2::Solver& S = *s->s;
+    S.pen_need("penalty");
+    S.pen.set(S.view(nullptr), S.topo.vol, S.pen_limit(), sigma, forch, target, n);
+  });
+}
+cfd_status cfd_set_penalty_scale(cfd_solver* s, float target_scale) {
+  CHECK_S(s);
+  return guard([&] {
+    s->s->pen_need("penalty scale");
+    s->s->pen.set_scale(target_scale);
+  });
+}
+cfd_status cfd_get_penalty(cfd_solver* s, cfd_penalty_info* info, float* sigma, float* forch, float* target) {
+  CHECK_S(s);
+  return guard([&] {
+    cfd2::Solver& S = *s->s;
+    if (info) {  // a read: answered on every handle (no field can be set where set_penalty refuses)
+      std::memset(info, 0, sizeof(*info));
+      info->active = S.pen.on() ? 1 : 0;
+      info->has_forch = S.pen.has_forch ? 1 : 0;
+      info->has_target = S.pen.has_target ? 1 : 0;
+      info->target_scale = S.pen.scale;
+      info->max_vol_sigma = S.pen_limit();
+    }
+    if (sigma || forch || target) S.pen.get(S.view(nullptr), sigma, forch, target);
+  });
+}
+cfd_status cfd_penalty_force_get(cfd_solver* s, double cx, double cy, const double* box, cfd_penalty_force* out) {
+  CHECK_S(s);
+  if (!out) return set_error(CFD_ERR_INVALID, "null out");
+  return guard([&] {
+    cfd2::Solver& S = *s->s;
+    S.pen_need("penalty force");
+    S.pen.force(S.view(nullptr), S.cell_cx, S.cell_cy, cx, cy, box, out);
+  });
+}
+
 // ------------------------------------------------------- frames on the device
 cfd_status cfd_render_set_polygons(cfd_solver* s, uint32_t num_vertices, const double* vx, const double* vy,
                                    const uint32_t* cell_vertex_offsets, const uint32_t* cell_vertices) {

@@ -19,6 +19,9 @@ void Solver::set_reference_semantics(int flags) {
   if ((flags & (1 | 2)) && visc.on())
     throw std::invalid_argument("reference semantics: the racy prepare and the in-place smoother have no form with a "
                                 "viscosity field (clear it first)");
+  if ((flags & (1 | 2)) && pen.on())
+    throw std::invalid_argument("reference semantics: the racy prepare and the in-place smoother have no form with "
+                                "volume penalisation (clear it first)");
   if ((flags & 2) && !d_flux_mirror) {  // each non-owner face slot -> the owner's slot of that face
     const size_t S = (size_t)topo.wf * N;
     size_t nfaces = 0;  // unused slots hold 0xFFFFFFFF: not a face

@@ -1,5 +1,5 @@
 // What an opt-in feature (the post-processing modules of modules.hpp, Scalars,
-// BoundaryVelocity, Viscosity) may read of the solver: one value, built fresh by
+// BoundaryVelocity, Viscosity, Penalty) may read of the solver: one value, built fresh by
 // Solver::view for every call (the ring rotates), of const members and
 // pointers to const.  A method of theirs takes it first and has no other way
 // to the solver's state.

@@ -239,6 +239,7 @@ Solver::~Solver() {
   bcv.arena.release();
   bcv.wm_arena.release();
   visc.arena.release();
+  pen.arena.release();
   amg_arena.release();
   scalars.arena.release();
   if (cstream) (void)hipStreamDestroy(cstream);
@@ -360,7 +361,9 @@ void Solver::prepare() {
     return;
   }
   const BcvArgs v = bcv.args();
-  if (visc.on())  // variable viscosity (viscosity.cpp): the VISC forms only with a field
+  if (pen.on())  // volume penalisation (penalty.cpp): the PEN form of whichever of the four is on
+    launch_prepare_pen(a, bcv.on() ? &v : nullptr, visc.mu, pen.args(), stream);
+  else if (visc.on())  // variable viscosity (viscosity.cpp): the VISC forms only with a field
     launch_prepare_visc(a, bcv.on() ? &v : nullptr, visc.mu, stream);
   else if (bcv.on())  // prescribed boundary velocities (boundary_velocity.cpp): the BCV form only with a selection
     launch_prepare_bcv(a, v, stream);
@@ -401,7 +404,9 @@ void Solver::assemble() {
   BuoyancyArgs b;
   const bool buoyant = scalars.buoyancy_args(b);
   const BcvArgs v = bcv.args();
-  if (visc.on())  // variable viscosity: the VISC form of any of the four
+  if (pen.on())  // volume penalisation: the PEN form of any of the eight
+    launch_assemble_pen(a, buoyant ? &b : nullptr, bcv.on() ? &v : nullptr, visc.mu, pen.args(), stream);
+  else if (visc.on())  // variable viscosity: the VISC form of any of the four
     launch_assemble_visc(a, buoyant ? &b : nullptr, bcv.on() ? &v : nullptr, visc.mu, stream);
   else if (bcv.on())  // prescribed boundary velocities: the BCV form of either
     launch_assemble_bcv(a, buoyant ? &b : nullptr, v, stream);

@@ -19,6 +19,7 @@
 #include "device_mem.hpp"
 #include "dist.hpp"
 #include "modules.hpp"
+#include "penalty.hpp"
 #include "scalars.hpp"
 #include "topology.hpp"
 #include "tuning.hpp"
@@ -469,6 +470,20 @@ struct Solver {
   // what BoundaryVelocity's calls refuse first: ref_racy stays private
   void bcv_need(const char* what) const { BoundaryVelocity::need(what, dist(), ref_racy); }
   void visc_need(const char* what) const { Viscosity::need(what, dist(), ref_racy || ref_inplace); }
+  // volume penalisation (penalty.hpp): prepare() and assemble() take the PEN forms when pen.on()
+  Penalty pen;
+  void pen_need(const char* what) const { Penalty::need(what, dist(), ref_racy || ref_inplace); }
+  // the largest vol * sigma cfd_set_penalty takes on this handle, with the density as it stands
+  // (the walk over the face slots is made once: the mesh does not change)
+  double pen_limit() {
+    if (!pen_geom_known) {
+      pen_geom = penalty_geometry(topo);
+      pen_geom_known = true;
+    }
+    return penalty_limit(pen_geom, constants.density);
+  }
+  PenaltyGeometry pen_geom;
+  bool pen_geom_known = false;
   // ---- the opt-in post-processing modules (modules.hpp) ----
   // Each reads the solver through view() alone; nothing of theirs is allocated
   // before their first enabling call, and step() launches none of it.

@@ -1145,6 +1145,120 @@ cfd_status cfd_viscosity_stats_get(cfd_solver* s, cfd_viscosity_stats* out);
 cfd_status cfd_debug_pow_det(const double* x, const double* y, double* out, uint32_t n);
 
 /* ------------------------------------------------------------------------ */
+/* Volume penalisation: a term in the momentum equation that acts inside the
+ * fluid.  Every cell gets a linear drag towards a target velocity,
+ *   rho du/dt + ... = ... - s (u - u_t),     s = sigma + forch |u|
+ * sigma large and u_t = 0: the cell behaves as a solid (Brinkman
+ * penalisation); sigma moderate: a Darcy porous medium, forch adding the
+ * Forchheimer quadratic drag; u_t != 0: a body that moves or rotates through
+ * the fixed mesh; sigma rising towards the outlet: a sponge layer.  The term is
+ * diagonal and implicit.  Opt-in: without a field (the default, and again after
+ * a clear) cfd_step launches the kernels it always launched, with the same
+ * arguments, and produces the same bits; with one, prepare_coupled and the
+ * assembly run in their PEN forms, which read 4 more bytes per cell (sigma), 4
+ * more with forch and, in the assembly, 8 more with a target, all coalesced.
+ *
+ * Arithmetic of volume penalisation.  All f32, one rounding per operation
+ * (nothing fused), in this order, for cell i; uc = u[i] of the current iterate,
+ * the velocity both kernels already load:
+ *   s   = sigma[i]                                              forch null
+ *   s   = sigma[i] + forch[i] * sqrtf(uc.x*uc.x + uc.y*uc.y)    forch set
+ *   pen = vol[i] * s
+ *   prepare_coupled: diag_coeff += pen    after the face loop, before d_p = vol / diag_coeff
+ *   assembly:        diag_uv    += pen    after the face loop and the buoyancy term
+ *                    rhs_u      += pen * (target_scale * target[i].x)
+ *                    rhs_v      += pen * (target_scale * target[i].y)
+ * With a null target nothing is added to the right-hand side (not even +0).
+ * Because forch reads the iterate, the quadratic drag is re-evaluated at every
+ * Picard iteration at no extra cost; prepare_coupled and the assembly of one
+ * iteration read the same state, so d_p and the momentum diagonal agree, and
+ * the Rhie-Chow flux and the pressure Laplacian see the drag through d_p with
+ * no change of their own.  Nothing else in either kernel changes: no
+ * off-diagonal momentum coefficient changes bits.  sigma == 0 everywhere with
+ * null forch and target gives the plain step's bits: the diagonals are
+ * positive and x + 0.0f == x (no -0 exception is known: neither diagonal can
+ * be -0, a sum that starts from the positive time coefficient).
+ * The pointers the kernels read stay the same while a field is set, and they
+ * read the contents when they run: replacing the field between steps is one
+ * upload, also when the Krylov iteration replays a captured graph;
+ * target_scale is a kernel argument, so an oscillating body costs no upload.
+ *
+ * The limit on vol * sigma.  The pressure row of cell i has the diagonal
+ *   sdiag_i = sum over its interior and outlet slots of density * dp_f * area / dist
+ * with dp_f = lambda d_p[i] + (1 - lambda) d_p[other], lambda in [0, 1] (d_p[i]
+ * on an outlet slot), and the preconditioner takes 1 / sdiag_i only when
+ * |sdiag_i| > 1e-14, else 0.  So sdiag_i >= density * G_i * min d_p, with G_i
+ * the sum of area / dist over those slots, the minimum over cell i and its
+ * neighbours.  d_p[j] = vol_j / (B_j + pen_j), B_j the plain diagonal; where the
+ * penalty dominates (pen_j >= B_j) d_p[j] >= vol_j / (2 pen_j).  With pen_j <= L
+ * everywhere, the penalty alone cannot push a pressure diagonal under the
+ * threshold when  density * min(G) * min(vol) / (2 L) > 1e-14.  With a further
+ * factor 2 of margin, on this handle's mesh and with the density as it stands
+ * at the call,
+ *   L = density * min_i(G_i) * min_i(vol_i) / 4e-14
+ * and cfd_set_penalty refuses a field with vol[i] * sigma[i] > L for any cell
+ * (cfd_penalty_info::max_vol_sigma reports L).  On a uniform mesh of spacing h
+ * with density 1, G = 4 and L = 1e14 h^2, that is sigma <= 1e14.  The limit is
+ * on the uploaded sigma: the Forchheimer part forch |u| is part of the state and
+ * is not bounded by it; lowering the density afterwards lowers the margin in
+ * proportion.  Where B_j dominates, d_p is within a factor 2 of the plain
+ * solver's and the penalty is not what makes it small.
+ *
+ * The force diagnostic.  cfd_penalty_force_get makes one read-only pass over
+ * the current state, per cell in f64 (every f32 value widened first, one
+ * rounding per operation):
+ *   s  = sigma + forch * sqrt(ux*ux + uy*uy)       (forch null: s = sigma)
+ *   m  = vol * s;   tx = target_scale * target.x,  ty = target_scale * target.y   (null: 0, 0)
+ *   fx = m * (ux - tx);   fy = m * (uy - ty)
+ *   F = sum (fx, fy)                    the force of the fluid on the penalised medium
+ *   tau = sum rx * fy - ry * fx         r = the f64 cell centre - (cx, cy)
+ *   P = sum fx * tx + fy * ty           the rate of work of that force on the moving medium
+ *                                       (negative where the body drives the fluid: the body delivers -P)
+ *   n = cells with s > 0
+ * each sum in the canonical leaf / chunk / segment / total order of the other
+ * f64 diagnostics, so the bits do not depend on the scheduling.  With a box the
+ * sums run over the cells whose f64 centre lies in the closed box (the force
+ * region's rule: x0 <= x <= x1 and y0 <= y <= y1, none for x1 < x0), so two
+ * bodies can be read separately.  It is the drag and lift of an immersed body,
+ * the counterpart of cfd_flow_diagnostics' wall force, and the term that closes
+ * a momentum budget beside it and cfd_buoyancy_force_get.
+ * Checkpoints store none of this (the file format and its version are
+ * unchanged): a resumed run sets the field and the scale again.  One GPU only,
+ * and not together with flags 1 or 2 of cfd_debug_reference_semantics.       */
+typedef struct cfd_penalty_info {
+  int32_t active;        /* a field is set */
+  int32_t has_forch, has_target;
+  float target_scale;    /* 1 until cfd_set_penalty_scale */
+  double max_vol_sigma;  /* L above, with the density as it stands */
+} cfd_penalty_info;
+typedef struct cfd_penalty_force {
+  double force[2];
+  double torque;
+  double power;
+  uint32_t cells;        /* with s > 0 (inside the box) */
+  uint32_t reserved;
+} cfd_penalty_force;
+/* sigma[n], forch[n] or null, target[2 n] (x, y per cell) or null.
+ * n == num_cells: sets or replaces the field (one upload; the device pointers
+ * stay); n == 0 clears it (the pointers may be null).  Every value is checked
+ * before anything changes.  CFD_ERR_INVALID: any other n; a value that is not
+ * finite; a negative sigma or forch; max(vol) * max(sigma) not finite in f32;
+ * vol[i] * sigma[i] above the limit L; a distributed handle; reference
+ * semantics with flag 1 or 2.  A refused call changes nothing.                */
+cfd_status cfd_set_penalty(cfd_solver* s, const float* sigma, const float* forch, const float* target, uint32_t n);
+/* target_scale (finite), a kernel argument of the next launches; may be set
+ * before a field; survives a clear.                                           */
+cfd_status cfd_set_penalty_scale(cfd_solver* s, float target_scale);
+/* info and the arrays are optional (null: skipped).  A read: info is answered on
+ * every handle, also a distributed one and in the reference-semantics modes,
+ * where no field can be set and active is 0.  CFD_ERR_INVALID: an array asked
+ * for without a field, forch or target asked for when none is set.            */
+cfd_status cfd_get_penalty(cfd_solver* s, cfd_penalty_info* info, float* sigma, float* forch, float* target);
+/* box: {x0, y0, x1, y1} or null (every cell).  Read-only.  CFD_ERR_INVALID: no
+ * field is set, cx or cy not finite, a NaN in the box, a distributed handle.   */
+cfd_status cfd_penalty_force_get(cfd_solver* s, double cx, double cy, const double* box, cfd_penalty_force* out);
+
+/* ------------------------------------------------------------------------ */
 /* Frames on the device: a cell field as an H x W RGBA8 image, the headless
  * form of the reference's renderer (src/ui/cfd_renderer.rs fan-triangulates
  * every cell, cfd_mesh_shader.wgsl colours each fan by the cell's value).  The
